@@ -13,7 +13,7 @@ test-gpu:         ## parity of every kernel through the C-ABI (needs an MI355X)
 	$(PY) -m pytest tests -x -q -m gpu
 
 bench:            ## one JSON line: GF(2^8) multiply, 1e8 elements, roofline + CPU baseline
-	$(PY) bench.py
+	$(PY) bench.py --full
 
 c-host:           ## the plain-C host example over include/galois_amd.h
 	gcc -std=c99 -Wall -D__HIP_PLATFORM_AMD__ -Iinclude -I/opt/rocm/include examples/c_host_rs.c \

@@ -2,7 +2,7 @@
 """
 bench.py -- headline benchmark of the finite-field hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: launched by torch.distributed.run, one rank per GPU; RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* from the env)
 
 Workload (BASELINE.json configs[1]): GF(2^8) multiply, EXP/LOG-class lookup mode (full LDS product table), 1e8 uint8
@@ -10,11 +10,16 @@ elements PER GPU, inputs resident in HBM (x: seed 1, y: seed 2, as SURVEY.md sec
 np.multiply over the 1e8-element batch through the C-ABI (gfa_binary).  Weak scaling: every rank owns an independent
 1e8-element shard; there is no data-path collective, only the timing barrier and a MAX all-reduce of the elapsed time.
 
-One JSON line is printed by rank 0.  Besides the contract keys it carries
+A plain run sets up, warms up, times the K steps and prints one JSON line (rank 0) with the headline figure.
+--dump-outputs DIR writes the product of the last timed step as DIR/gf256_mul.npy (DIR/gf256_mul_rank<r>.npy at N > 1):
+float32, the elements at a fixed, seeded sample of 2^23 / N positions (sorted, duplicates dropped) of each rank's shard.
+--full also runs everything else, after the timed region, and adds to the line
+  "as_measured_without_prewarm": 5 + 20 steps straight after set-up, before the clock pre-warm
   "roofline":     dominant kernel (tab8_binary_kernel) -- algorithmic 3 B/element x 1e8 per launch / HIP-event time
   "cpu_baseline": the C port of the reference's lookup ufunc (oracle/gf_oracle.c, 1 thread) on the same data
   "extra":        the other two parts of BASELINE.json's composite metric (2^20-point NTT/s, RS(255,223) GB/s),
                   measured after the timed region on this rank's GPU, each with its own roofline fraction.
+and checks the headline product against the oracle.
 """
 import argparse
 import ctypes
@@ -40,6 +45,10 @@ def main():
     # defaults: ~0.1 s of warm-up steps and ~0.1 s timed (wall clock around 20 steps = 1 ms carries the launch / sync latency)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=2000)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write a seeded sample of the last timed step's product to DIR as .npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything besides the headline figure (see the module docstring); "
+                         "the --no-* and --dist-extras options below apply to it")
     ap.add_argument("--no-extras", action="store_true", help="skip the NTT / Reed-Solomon side measurements")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="do not run the two rocprofv3 --pmc passes that measure the HBM traffic")
@@ -48,6 +57,8 @@ def main():
     ap.add_argument("--print-launch", action="store_true",
                     help="print the torch.distributed.run command `--gpus N` re-executes itself under, and exit")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` with no launcher around it: start the N ranks ourselves (one process per GPU over RCCL)
@@ -64,7 +75,7 @@ def main():
         local_rank = int(os.environ["GFA_BENCH_SINGLE_DEVICE"])
     torch.cuda.set_device(local_rank)
     dist = None
-    if world > 1 or args.dist_extras:
+    if world > 1 or (args.full and args.dist_extras):
         import torch.distributed as dist
 
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -104,16 +115,17 @@ def main():
         if rc:
             L.check(rc, "gfa_binary")
 
-    # As-measured figure with the protocol of rounds 1-3 (5 warm-up + 20 timed steps straight after the idle set-up phase, no clock
-    # pre-warm): kept NEXT to the warm figure so that rounds stay comparable
-    for _ in range(5):
-        step()
-    torch.cuda.synchronize()
-    t_cold = time.perf_counter()
-    for _ in range(20):
-        step()
-    torch.cuda.synchronize()
-    cold_elapsed = time.perf_counter() - t_cold
+    if args.full:
+        # As-measured figure with the protocol of rounds 1-3 (5 warm-up + 20 timed steps straight after the idle set-up phase, no
+        # clock pre-warm): kept NEXT to the warm figure so that rounds stay comparable
+        for _ in range(5):
+            step()
+        torch.cuda.synchronize()
+        t_cold = time.perf_counter()
+        for _ in range(20):
+            step()
+        torch.cuda.synchronize()
+        cold_elapsed = time.perf_counter() - t_cold
 
     # Clock pre-warm, untimed and outside the W + K steps: the set-up above leaves the GPU idle for seconds, and it then needs tens
     # of milliseconds of load before its clocks are back up -- a kernel timed straight away reads 3-15 % slow
@@ -143,7 +155,39 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank, world)
 
+    result = None
+    if rank == 0:
+        value = world * n * args.steps / elapsed / 1e9
+        result = {
+            "metric": "GF(2^8) mul Gop/s (lookup mode, 1e8 uint8 per GPU)",
+            "value": round(value, 2),
+            "unit": "Gop/s",
+            "n_gpus": world,
+            "rccl_ranks": (dist.get_world_size() if dist is not None else 1),
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "clock_prewarm": {"steps": prewarm_steps, "ms": round(prewarm_ms, 1), "timed": False},
+            "ms_per_step": round(elapsed / args.steps * 1e3, 5),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "u8",
+            "data": "synthetic",
+            "config": {"workload": "GF(2^8) mul, lookup mode, 1e8 uint8 per GPU, poly 0x11D (BASELINE.json configs[1])",
+                       "elements_per_gpu": n, "parallelism": f"batch-shard x{world}, no collectives"},
+        }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # ---- --full from here on: checks and measurements besides the headline figure ----
     # parity gate on this rank's shard (sampled every 997th element + both ends) against the oracle port
     from oracle import gf_oracle as O
 
@@ -175,29 +219,9 @@ def main():
                 "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_live": bool(traffic_source and traffic_source.startswith("live")),
                 "kernel": "tab8_binary_kernel", "kernel_ms": round(ms.value, 5), "algorithmic_bytes_per_launch": alg_bytes}
 
-    result = None
     if rank == 0:
-        value = world * n * args.steps / elapsed / 1e9
-        result = {
-            "metric": "GF(2^8) mul Gop/s (lookup mode, 1e8 uint8 per GPU)",
-            "value": round(value, 2),
-            "unit": "Gop/s",
-            "n_gpus": world,
-            "rccl_ranks": (dist.get_world_size() if dist is not None else 1),
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "clock_prewarm": {"steps": prewarm_steps, "ms": round(prewarm_ms, 1), "timed": False},
-            "as_measured_without_prewarm": {"value": round(n * 20 / cold_elapsed / 1e9, 2), "unit": "Gop/s", "steps": 20, "warmup": 5},
-            "ms_per_step": round(elapsed / args.steps * 1e3, 5),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": "synthetic",
-            "config": {"workload": "GF(2^8) mul, lookup mode, 1e8 uint8 per GPU, poly 0x11D (BASELINE.json configs[1])",
-                       "elements_per_gpu": n, "parallelism": f"batch-shard x{world}, no collectives"},
-            "roofline": roofline,
-        }
+        result["as_measured_without_prewarm"] = {"value": round(n * 20 / cold_elapsed / 1e9, 2), "unit": "Gop/s", "steps": 20, "warmup": 5}
+        result["roofline"] = roofline
 
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         # bounded CPU sample: the same 1e8-element batch, repeated until >= 10 s of single-thread work
@@ -277,6 +301,22 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE = 1 << 23  # positions over all ranks: 32 MiB of float32 at most
+DUMP_SEED = 20240901
+
+
+def dump_outputs(out_dir, out, rank, world):
+    """The product of the last timed step at a fixed, seeded sample of positions of this rank's shard, as float32 .npy
+    (the whole 1e8-element product would be 400 MB in float32).  The inputs are seeded too, so two builds of the project
+    compare file for file."""
+    n = out.numel()
+    idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_SAMPLE // world))
+    vals = out.cpu().numpy()[idx].astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    name = "gf256_mul.npy" if world == 1 else f"gf256_mul_rank{rank}.npy"
+    np.save(os.path.join(out_dir, name), vals)
 
 
 def self_launch(args):

@@ -13,6 +13,8 @@ Two sources, both the reference's own:
      /root/reference/src in its pure-Python mode (oracle/ref_shim), for the configurations that have no upstream
      fixture: NTTs over GF(65537) / GF(7340033) / Goldilocks (+ the four SymPy KATs of tests/fields/test_ntt.py:13-18),
      RS(255,223) encode/decode incl. erasures and uncorrectable words, GF(2^8)/GF(31)/Goldilocks element-wise samples.
+  3. tests/golden/reference_live.json -- the reference's side of tests/test_oracle_vs_reference.py, recorded by running that
+     module against the reference (`reference_live`; see the module's docstring).
 """
 import glob
 import json
@@ -539,8 +541,17 @@ def reference_table_fields():
     np.savez_compressed(os.path.join(OUT_DIR, "reference_table_fields.npz"), **out)
 
 
+def reference_live():
+    import subprocess
+
+    env = dict(os.environ, GOLDEN_RECORD_REFERENCE="1", GOLDEN_OUT=OUT_DIR)
+    subprocess.run([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider", os.path.join(ROOT, "tests", "test_oracle_vs_reference.py")],
+                   env=env, cwd=ROOT, check=True)
+
+
 if __name__ == "__main__":
-    what = sys.argv[1:] or ["fields", "rs", "reference", "bch", "reference_bch", "reference_wide", "reference_tables", "linalg", "polys"]
+    what = sys.argv[1:] or ["fields", "rs", "reference", "bch", "reference_bch", "reference_wide", "reference_tables", "linalg", "polys",
+                            "reference_live"]
     if "fields" in what:
         pack_sage_fields()
         pack_sage_wide_fields()
@@ -561,4 +572,6 @@ if __name__ == "__main__":
         reference_wide_codes()
     if "reference_tables" in what:
         reference_table_fields()
+    if "reference_live" in what:
+        reference_live()
     print("done")

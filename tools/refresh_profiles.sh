@@ -10,19 +10,19 @@ OUT=$ROOT/gpurun_out
 mkdir -p "$OUT"
 cd "$ROOT"
 if [ "$ONLY" = codes ]; then
-    python bench.py > "$OUT/${R}_bench_final.json" 2> "$OUT/${R}_bench_final.err"
+    python bench.py --full > "$OUT/${R}_bench_final.json" 2> "$OUT/${R}_bench_final.err"
     python tools/goldi_time.py 2>/dev/null | grep "2^" > "$OUT/${R}_ntt_goldilocks.txt"
     python tools/rs_time.py 2>/dev/null | tail -1 > "$OUT/${R}_rs_time.txt"
     python tools/ntt_large.py 20 21 22 24 26 28 > "$OUT/${R}_ntt_large.txt" 2>/dev/null
-    ( cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/prof_$R && rocprofv3 --kernel-trace --stats -d /tmp/prof_$R -o bench -- python "$ROOT/bench.py" --no-cpu-baseline --no-pmc > /dev/null 2>&1
+    ( cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/prof_$R && rocprofv3 --kernel-trace --stats -d /tmp/prof_$R -o bench -- python "$ROOT/bench.py" --full --no-cpu-baseline --no-pmc > /dev/null 2>&1
       DB=$(find /tmp/prof_$R -name "*.db" | head -1); [ -n "$DB" ] && python "$ROOT/tools/export_rocprof_stats.py" "$DB" "$OUT/${R}_bench_kernel_stats.csv" )
     bash tools/pmc_run.sh ${R}_pmc_ntt_goldilocks ntt_reg_kernel_gl -- python tools/goldi_time.py > /dev/null 2>&1
     bash tools/pmc_run.sh ${R}_pmc_rs_decode rs_ -- python tools/rs_decode_only.py 5 > /dev/null 2>&1
     ls -la "$OUT" | tail -12
     exit 0
 fi
-python bench.py > "$OUT/${R}_bench_final.json" 2> "$OUT/${R}_bench_final.err"
-python bench.py --steps 50 --warmup 5 --dist-extras --no-cpu-baseline --no-pmc > "$OUT/${R}_bench_dist_world1.json" 2>/dev/null
+python bench.py --full > "$OUT/${R}_bench_final.json" 2> "$OUT/${R}_bench_final.err"
+python bench.py --full --steps 50 --warmup 5 --dist-extras --no-cpu-baseline --no-pmc > "$OUT/${R}_bench_dist_world1.json" 2>/dev/null
 python tools/ew_bench.py 2>/dev/null | grep field > "$OUT/${R}_ew_bench.txt"
 python tools/fermat_time.py 64 256 1024 4096 2>/dev/null | grep batch > "$OUT/${R}_ntt_fermat_batches.txt"
 python tools/fermat_phases.py 1024 2>/dev/null | grep -E "round|phase|spread" > "$OUT/${R}_ntt_fermat_phases.txt"
@@ -42,7 +42,7 @@ python tools/ntt_large.py 20 21 22 24 26 28 > "$OUT/${R}_ntt_large.txt" 2>/dev/n
 python tools/fft_small_bench.py 2>/dev/null | grep size > "$OUT/${R}_fft_reference_benchmark_sizes.txt"
 python tools/wide_codes_bench.py > "$OUT/${R}_wide_codes_bench.txt" 2>/dev/null
 python tools/linalg_bench.py > "$OUT/${R}_linalg_bench.txt" 2>/dev/null
-( cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/prof_$R && rocprofv3 --kernel-trace --stats -d /tmp/prof_$R -o bench -- python "$ROOT/bench.py" --no-cpu-baseline --no-pmc > /dev/null 2>&1
+( cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/prof_$R && rocprofv3 --kernel-trace --stats -d /tmp/prof_$R -o bench -- python "$ROOT/bench.py" --full --no-cpu-baseline --no-pmc > /dev/null 2>&1
   DB=$(find /tmp/prof_$R -name "*.db" | head -1); [ -n "$DB" ] && python "$ROOT/tools/export_rocprof_stats.py" "$DB" "$OUT/${R}_bench_kernel_stats.csv" )
 bash tools/pmc_run.sh ${R}_pmc_headline tab8_binary -- python tools/headline_only.py 6 > /dev/null 2>&1
 bash tools/pmc_run.sh ${R}_pmc_ntt_fermat ntt_fermat16 -- python tools/fermat_time.py 1024 > /dev/null 2>&1
