@@ -27,31 +27,9 @@ struct alignas(16) Vec16 {
     T v[N];
 };
 
-__device__ __forceinline__ void flag_error(int32_t *err, bool bad)
-{
-    // one atomic per wave at most
-    if (__any(bad)) {
-        if ((threadIdx.x & 63) == 0 && err) atomicOr(err, GFA_DEVERR_ZERO_DIVISION);
-    }
-}
-
 // ------------------------------------------------------------------------------------------------
 // Generic element-wise kernels
 // ------------------------------------------------------------------------------------------------
-template <class F, int OP>
-__device__ __forceinline__ typename F::elem apply_binary(const FieldDev &fd, typename F::elem x, typename F::elem y, bool &bad)
-{
-    if constexpr (OP == GFA_OP_ADD) return F::add(fd, x, y);
-    else if constexpr (OP == GFA_OP_SUB) return F::sub(fd, x, y);
-    else if constexpr (OP == GFA_OP_MUL) return F::mul(fd, x, y);
-    else { // DIV: reciprocal of the divisor then multiply (divide_ufunc.__call__, _ufunc.py:433-437)
-        if (y == 0) { bad = true; return 0; }
-        if (x == 0) return 0;
-        if constexpr (std::is_same<F, Lut>::value) return Lut::div_nz(fd, x, y);
-        else return F::mul(fd, x, F::inv(fd, y));
-    }
-}
-
 template <class F, int OP>
 __device__ __forceinline__ typename F::elem apply_unary(const FieldDev &fd, typename F::elem x, bool &bad)
 {
@@ -611,39 +589,6 @@ __global__ __launch_bounds__(TAB8_THREADS) void tab8_unary_kernel(const uint8_t 
 // ------------------------------------------------------------------------------------------------
 // launch helpers
 // ------------------------------------------------------------------------------------------------
-int num_cus()
-{
-    static int cached[64] = {0};
-    int d = 0;
-    if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) return 256;
-    if (!cached[d]) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, d) != hipSuccess) return 256;
-        cached[d] = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
-    return cached[d];
-}
-
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-inline int grid_for(i64 work_items, int threads, int blocks_per_cu)
-{
-    i64 blocks = (work_items + threads - 1) / threads;
-    i64 cap = (i64)num_cus() * blocks_per_cu;
-    if (blocks < 1) blocks = 1;
-    return (int)(blocks < cap ? blocks : cap);
-}
-
-// Streaming kernels without per-workgroup set-up are launched FLAT (one 16-byte vector per thread).  With a persistent
-// grid-stride launch the workgroups drift apart, the active address window spreads and HBM efficiency drops once the
-// arrays exceed the Infinity Cache: 5.0 vs 6.0-6.6 TB/s on 1e9-byte operands (tools/ubench/stream_big.hip).
-inline int grid_flat(i64 work_items, int threads)
-{
-    i64 blocks = (work_items + threads - 1) / threads;
-    if (blocks < 1) blocks = 1;
-    return (int)(blocks < 0x7fffffff ? blocks : 0x7fffffff);
-}
-
 template <class F, typename T>
 int launch_binary_ft(const FieldDev &fd, int op, const void *a, i64 sa, const void *b, i64 sb, void *out, i64 n,
                      hipStream_t st, int32_t *err)
@@ -947,492 +892,6 @@ int dispatch_intarg(const FieldDev &fd, int dtype, bool is_pow, const void *a, i
     GFA_DISPATCH_FT(launch_intarg_ft, fd, dtype, fd, is_pow, a, sa, e, se, out, n, st, err);
 }
 
-
-// ------------------------------------------------------------------------------------------------
-// ufunc.reduce over the last axis (add / multiply are commutative monoids -> tree reduction; subtract / divide are
-// the reference's left folds a0 - a1 - ... = a0 - sum(rest), a0 / a1 / ... = a0 / prod(rest))
-// ------------------------------------------------------------------------------------------------
-template <class F, typename T, bool IS_MUL>
-__global__ __launch_bounds__(256) void reduce_segments_kernel(FieldDev fd, const T *__restrict__ in, i64 n_inner,
-                                                              i64 col_begin, i64 seg_len, i64 nseg,
-                                                              u64 *__restrict__ partial)
-{
-    typedef typename F::elem E;
-    __shared__ u64 sh[256];
-    const i64 row = blockIdx.x / nseg, seg = blockIdx.x % nseg;
-    const i64 lo = col_begin + seg * seg_len;
-    i64 hi = lo + seg_len;
-    if (hi > n_inner) hi = n_inner;
-    const T *x = in + row * n_inner;
-    E acc = IS_MUL ? F::one(fd) : (E)0;
-    for (i64 i = lo + threadIdx.x; i < hi; i += 256) {
-        E v = (E)x[i];
-        acc = IS_MUL ? F::mul(fd, acc, v) : F::add(fd, acc, v);
-    }
-    sh[threadIdx.x] = (u64)acc;
-    __syncthreads();
-    for (int off = 128; off >= 1; off >>= 1) {
-        if ((int)threadIdx.x < off) {
-            E a = (E)sh[threadIdx.x], b = (E)sh[threadIdx.x + off];
-            sh[threadIdx.x] = (u64)(IS_MUL ? F::mul(fd, a, b) : F::add(fd, a, b));
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = sh[0];
-}
-
-// mode 0: out = reduce(partials); 1: out = a0 - sum(partials); 2: out = a0 / prod(partials)
-template <class F, typename T, bool IS_MUL>
-__global__ void reduce_finalize_kernel(FieldDev fd, const T *__restrict__ in, i64 n_inner, const u64 *__restrict__ partial,
-                                       i64 nseg, T *__restrict__ out, i64 n_outer, int mode, int32_t *err)
-{
-    typedef typename F::elem E;
-    const i64 row = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-    bool bad = false;
-    if (row < n_outer) {
-        E acc = IS_MUL ? F::one(fd) : (E)0;
-        for (i64 s = 0; s < nseg; s++) {
-            E v = (E)partial[row * nseg + s];
-            acc = IS_MUL ? F::mul(fd, acc, v) : F::add(fd, acc, v);
-        }
-        if (mode == 1) acc = F::sub(fd, (E)in[row * n_inner], acc);
-        if (mode == 2) {
-            E a0 = (E)in[row * n_inner];
-            if (acc == 0) { bad = true; acc = 0; }
-            else if (a0 == 0) acc = 0;
-            else {
-                if constexpr (std::is_same<F, Lut>::value) acc = Lut::div_nz(fd, a0, acc);
-                else acc = F::mul(fd, a0, F::inv(fd, acc));
-            }
-        }
-        out[row] = (T)acc;
-    }
-    flag_error(err, bad);
-}
-
-// ufunc.reduceat: out[s] = fold(a[starts[s] : ends[s]]) with NumPy's convention that an empty or reversed slice yields
-// a[starts[s]].  One 64-lane workgroup per segment; subtract / divide are left folds a0 - sum(rest), a0 / prod(rest).
-template <class F, typename T, bool IS_MUL>
-__global__ __launch_bounds__(64) void reduce_ragged_kernel(FieldDev fd, const T *__restrict__ in, const i64 *__restrict__ starts,
-                                                           const i64 *__restrict__ ends, T *__restrict__ out, int mode, int32_t *err)
-{
-    typedef typename F::elem E;
-    __shared__ u64 sh[64];
-    const i64 lo = starts[blockIdx.x];
-    i64 hi = ends[blockIdx.x];
-    if (hi <= lo) hi = lo + 1;
-    const i64 first = mode ? lo + 1 : lo;
-    E acc = IS_MUL ? F::one(fd) : (E)0;
-    for (i64 i = first + threadIdx.x; i < hi; i += 64) {
-        const E v = (E)in[i];
-        acc = IS_MUL ? F::mul(fd, acc, v) : F::add(fd, acc, v);
-    }
-    sh[threadIdx.x] = (u64)acc;
-    __syncthreads();
-    for (int off = 32; off >= 1; off >>= 1) {
-        if ((int)threadIdx.x < off) {
-            const E x = (E)sh[threadIdx.x], y = (E)sh[threadIdx.x + off];
-            sh[threadIdx.x] = (u64)(IS_MUL ? F::mul(fd, x, y) : F::add(fd, x, y));
-        }
-        __syncthreads();
-    }
-    bool bad = false;
-    if (threadIdx.x == 0) {
-        E r = (E)sh[0];
-        if (mode == 1) r = F::sub(fd, (E)in[lo], r);
-        if (mode == 2) {
-            const E a0 = (E)in[lo];
-            if (r == 0) { bad = true; r = 0; }
-            else if (a0 == 0) r = 0;
-            else {
-                if constexpr (std::is_same<F, Lut>::value) r = Lut::div_nz(fd, a0, r);
-                else r = F::mul(fd, a0, F::inv(fd, r));
-            }
-        }
-        out[blockIdx.x] = (T)r;
-    }
-    flag_error(err, bad);
-}
-
-template <class F, typename T>
-int launch_reduceat_ft(const FieldDev &fd, int op, const void *a, const i64 *starts, const i64 *ends, i64 nseg, void *out,
-                       hipStream_t st, int32_t *err)
-{
-    const bool is_mul = op == GFA_OP_MUL || op == GFA_OP_DIV;
-    const int mode = op == GFA_OP_SUB ? 1 : op == GFA_OP_DIV ? 2 : 0;
-    if (is_mul)
-        hipLaunchKernelGGL((reduce_ragged_kernel<F, T, true>), dim3((unsigned)nseg), dim3(64), 0, st, fd, (const T *)a, starts, ends,
-                           (T *)out, mode, err);
-    else
-        hipLaunchKernelGGL((reduce_ragged_kernel<F, T, false>), dim3((unsigned)nseg), dim3(64), 0, st, fd, (const T *)a, starts, ends,
-                           (T *)out, mode, err);
-    GFA_HIP(hipGetLastError());
-    return GFA_OK;
-}
-int dispatch_reduceat(const FieldDev &fd, int dtype, int op, const void *a, const i64 *starts, const i64 *ends, i64 nseg, void *out,
-                      hipStream_t st, int32_t *err)
-{
-    GFA_DISPATCH_FT(launch_reduceat_ft, fd, dtype, fd, op, a, starts, ends, nseg, out, st, err);
-}
-
-// ---- r06: streaming forms of the folds a 1-D array of 1e8 elements asks for (the generic kernel above reads one element per lane and load:
-// 0.04 of the roofline for np.add.reduce over GF(2^8)) ----
-// MODE 0: xor of the words (every field of characteristic 2: the fold of the elements is the fold of the packed words, folded once more
-//         across the word at the end).  MODE 1: plain integer sums in 64 bits, reduced mod p once per block (prime fields, elements of at
-//         most 32 bits: a block adds at most 2^32 of them).  MODE 2: np.multiply.reduce of a table field of at most 256 elements: sum of
-//         LOG[x] from a 256-entry LDS table, EXP once per block, zero if any element is zero.
-// Each block covers [lo, hi) of one row: 16-byte loads over the aligned middle, the unaligned head and tail element by element.
-template <typename T, int MODE>
-__global__ __launch_bounds__(256) void reduce_stream_kernel(const T *__restrict__ in, i64 n_inner, i64 col_begin, i64 seg_len, i64 nseg, u64 *__restrict__ partial,
-                                                            u64 p, const uint8_t *__restrict__ log8, const uint8_t *__restrict__ exp8, u32 qm1)
-{
-    __shared__ u64 sh[256];
-    __shared__ uint8_t lg[256];
-    __shared__ int any_zero;
-    extern __shared__ __attribute__((aligned(16))) uint8_t rs_add8[]; // MODE 3: the field's 64 KiB sum table (log8 points at it)
-    if (MODE == 3) {
-        const uint4 *s0 = reinterpret_cast<const uint4 *>(log8);
-        uint4 *d0 = reinterpret_cast<uint4 *>(rs_add8);
-        for (int i = threadIdx.x; i < 4096; i += 256) d0[i] = s0[i];
-        __syncthreads();
-    }
-    if (MODE == 2) {
-        lg[threadIdx.x] = log8[threadIdx.x];
-        if (threadIdx.x == 0) any_zero = 0;
-        __syncthreads();
-    }
-    constexpr int V = 16 / (int)sizeof(T);
-    const i64 row = blockIdx.x / nseg, seg = blockIdx.x % nseg;
-    const i64 lo = col_begin + seg * seg_len;
-    i64 hi = lo + seg_len;
-    if (hi > n_inner) hi = n_inner;
-    const T *x = in + row * n_inner;
-    u64 acc = 0;
-    u32 a4[4] = {0, 0, 0, 0}; // MODE 3: four chains of table additions per lane (independent gathers in flight)
-    bool zero = false;
-    auto one = [&](T v) {
-        if (MODE == 0) acc ^= (u64)v;
-        else if (MODE == 1) acc += (u64)v;
-        else if (MODE == 2) { zero |= v == 0; acc += (u64)lg[(uint8_t)v]; }
-        else a4[0] = rs_add8[(a4[0] << 8) | (u32)(uint8_t)v];
-    };
-    if (hi > lo) {
-        const uintptr_t addr = reinterpret_cast<uintptr_t>(x + lo);
-        i64 head = (i64)(((16 - (addr & 15)) & 15) / sizeof(T));
-        if (head > hi - lo) head = hi - lo;
-        const i64 a_lo = lo + head, nvec = (hi - a_lo) / V, a_hi = a_lo + nvec * V;
-        if ((i64)threadIdx.x < head) one(x[lo + threadIdx.x]);
-        if (a_hi + (i64)threadIdx.x < hi) one(x[a_hi + threadIdx.x]);
-        const uint4 *xv = reinterpret_cast<const uint4 *>(x + a_lo);
-        if (MODE == 0) {
-            u32 w0 = 0, w1 = 0, w2 = 0, w3 = 0;
-            for (i64 v = threadIdx.x; v < nvec; v += 256) { const uint4 w = xv[v]; w0 ^= w.x; w1 ^= w.y; w2 ^= w.z; w3 ^= w.w; }
-            u32 w = w0 ^ w1 ^ w2 ^ w3; // the elements of the four words sit at the same offsets inside a word (sizeof(T) divides 4), or T is 8 bytes
-            if (sizeof(T) == 8) acc ^= ((u64)(w1 ^ w3) << 32) | (u64)(w0 ^ w2);
-            else {
-                if (sizeof(T) <= 2) w ^= w >> 16;
-                if (sizeof(T) == 1) w ^= w >> 8;
-                acc ^= (u64)(w & (sizeof(T) == 1 ? 0xffu : sizeof(T) == 2 ? 0xffffu : 0xffffffffu));
-            }
-        } else {
-            for (i64 v = threadIdx.x; v < nvec; v += 256) {
-                const uint4 w = xv[v];
-                const u32 ww[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    if (sizeof(T) == 4) one((T)ww[j]);
-                    else if (sizeof(T) == 2) { one((T)(ww[j] & 0xffffu)); one((T)(ww[j] >> 16)); }
-                    else if (sizeof(T) == 1) {
-                        if (MODE == 3) { // static chain per byte lane of the word
-#pragma unroll
-                            for (int b = 0; b < 4; b++) a4[b] = rs_add8[(a4[b] << 8) | ((ww[j] >> (8 * b)) & 0xffu)];
-                        } else { one((T)(ww[j] & 0xffu)); one((T)((ww[j] >> 8) & 0xffu)); one((T)((ww[j] >> 16) & 0xffu)); one((T)(ww[j] >> 24)); }
-                    }
-                }
-                if (sizeof(T) == 8) { one((T)(((u64)w.y << 32) | w.x)); one((T)(((u64)w.w << 32) | w.z)); }
-            }
-        }
-    }
-    if (MODE == 2 && zero) any_zero = 1; // (benign race: every writer stores 1)
-    if (MODE == 3) {
-        u32 r = rs_add8[(a4[0] << 8) | a4[1]];
-        r = rs_add8[(r << 8) | a4[2]];
-        acc = rs_add8[(r << 8) | a4[3]];
-    }
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (int off = 128; off >= 1; off >>= 1) {
-        if ((int)threadIdx.x < off) {
-            if (MODE == 3) sh[threadIdx.x] = rs_add8[(sh[threadIdx.x] << 8) | sh[threadIdx.x + off]];
-            else sh[threadIdx.x] = MODE == 0 ? sh[threadIdx.x] ^ sh[threadIdx.x + off] : sh[threadIdx.x] + sh[threadIdx.x + off];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        u64 r = sh[0];
-        if (MODE == 1) r %= p;
-        if (MODE == 2) r = any_zero ? 0 : (u64)exp8[r % qm1];
-        partial[blockIdx.x] = r;
-    }
-}
-
-// the same finalisation with ONE WORKGROUP per row: a 1-D array is cut into up to 4096 segments, and one thread walking their partial results
-// was 180 of the 196 us np.add.reduce took over 1e8 bytes (r06)
-template <class F, typename T, bool IS_MUL>
-__global__ __launch_bounds__(256) void reduce_finalize_block_kernel(FieldDev fd, const T *__restrict__ in, i64 n_inner, const u64 *__restrict__ partial,
-                                                                    i64 nseg, T *__restrict__ out, int mode, int32_t *err)
-{
-    typedef typename F::elem E;
-    __shared__ u64 sh[256];
-    const i64 row = blockIdx.x;
-    E acc = IS_MUL ? F::one(fd) : (E)0;
-    for (i64 sg = threadIdx.x; sg < nseg; sg += 256) {
-        const E v = (E)partial[row * nseg + sg];
-        acc = IS_MUL ? F::mul(fd, acc, v) : F::add(fd, acc, v);
-    }
-    sh[threadIdx.x] = (u64)acc;
-    __syncthreads();
-    for (int off = 128; off >= 1; off >>= 1) {
-        if ((int)threadIdx.x < off) {
-            const E a = (E)sh[threadIdx.x], b = (E)sh[threadIdx.x + off];
-            sh[threadIdx.x] = (u64)(IS_MUL ? F::mul(fd, a, b) : F::add(fd, a, b));
-        }
-        __syncthreads();
-    }
-    bool bad = false;
-    if (threadIdx.x == 0) {
-        acc = (E)sh[0];
-        if (mode == 1) acc = F::sub(fd, (E)in[row * n_inner], acc);
-        if (mode == 2) {
-            const E a0 = (E)in[row * n_inner];
-            if (acc == 0) { bad = true; acc = 0; }
-            else if (a0 == 0) acc = 0;
-            else {
-                if constexpr (std::is_same<F, Lut>::value) acc = Lut::div_nz(fd, a0, acc);
-                else acc = F::mul(fd, a0, F::inv(fd, acc));
-            }
-        }
-        out[row] = (T)acc;
-    }
-    flag_error(err, bad);
-}
-
-struct ReduceScratch {
-    u64 *p = nullptr;
-    size_t n = 0;
-};
-ReduceScratch g_reduce_scratch[64];
-// byte LOG / EXP / sum table of the field a gfa_reduce / gfa_accumulate call is for (q <= 256; null otherwise)
-struct ByteTables {
-    const uint8_t *log8 = nullptr, *exp8 = nullptr, *add8 = nullptr;
-};
-
-// the fold of each of nseg segments of every row into partial[row * nseg + seg]: the streaming kernels where the fold is an xor of words / an
-// integer sum / a sum of byte logarithms (r06), else the generic kernel
-template <class F, typename T>
-void reduce_phase1(const FieldDev &fd, const ByteTables &bt, bool is_mul, const void *a, i64 n_inner, i64 col_begin, i64 seg_len, i64 nseg, i64 n_outer, u64 *partial,
-                   hipStream_t st)
-{
-    const unsigned grid = (unsigned)(n_outer * nseg);
-    int stream_mode = -1;
-    if (!is_mul && fd.p == 2) stream_mode = 0;
-    else if (!is_mul && fd.m == 1 && sizeof(T) <= 4 && seg_len < ((i64)1 << 32)) stream_mode = 1;
-    else if (is_mul && std::is_same<F, Lut>::value && sizeof(T) == 1 && fd.q <= 256 && bt.log8 && bt.exp8 && seg_len < ((i64)1 << 40)) stream_mode = 2;
-    else if (!is_mul && std::is_same<F, Lut>::value && sizeof(T) == 1 && fd.q <= 256 && fd.m > 1 && bt.add8) stream_mode = 3; // odd-characteristic table fields: the sum table in LDS
-    if (stream_mode == 0)
-        hipLaunchKernelGGL((reduce_stream_kernel<T, 0>), dim3(grid), dim3(256), 0, st, (const T *)a, n_inner, col_begin, seg_len, nseg, partial, (u64)fd.p, nullptr, nullptr, 0u);
-    else if (stream_mode == 1)
-        hipLaunchKernelGGL((reduce_stream_kernel<T, 1>), dim3(grid), dim3(256), 0, st, (const T *)a, n_inner, col_begin, seg_len, nseg, partial, (u64)fd.p, nullptr, nullptr, 0u);
-    else if (stream_mode == 2)
-        hipLaunchKernelGGL((reduce_stream_kernel<T, 2>), dim3(grid), dim3(256), 0, st, (const T *)a, n_inner, col_begin, seg_len, nseg, partial, (u64)fd.p, bt.log8,
-                           bt.exp8, (u32)(fd.q - 1));
-    else if (stream_mode == 3) {
-        static bool attr = false;
-        auto k3 = reduce_stream_kernel<T, 3>;
-        if (!attr) { (void)hipFuncSetAttribute((const void *)k3, hipFuncAttributeMaxDynamicSharedMemorySize, 65536); attr = true; }
-        hipLaunchKernelGGL(k3, dim3(grid), dim3(256), 65536, st, (const T *)a, n_inner, col_begin, seg_len, nseg, partial, (u64)fd.p, bt.add8, nullptr, 0u);
-    } else if (is_mul)
-        hipLaunchKernelGGL((reduce_segments_kernel<F, T, true>), dim3(grid), dim3(256), 0, st, fd, (const T *)a, n_inner, col_begin, seg_len, nseg, partial);
-    else
-        hipLaunchKernelGGL((reduce_segments_kernel<F, T, false>), dim3(grid), dim3(256), 0, st, fd, (const T *)a, n_inner, col_begin, seg_len, nseg, partial);
-}
-
-template <class F, typename T>
-int launch_reduce_ft(const FieldDev &fd, const ByteTables &bt, int op, const void *a, void *out, i64 n_outer, i64 n_inner, hipStream_t st,
-                     int32_t *err)
-{
-    const bool is_mul = op == GFA_OP_MUL || op == GFA_OP_DIV;
-    const int mode = op == GFA_OP_SUB ? 1 : op == GFA_OP_DIV ? 2 : 0;
-    const i64 col_begin = mode ? 1 : 0;
-    const i64 len = n_inner - col_begin;
-    // enough segments to fill the chip when there are few rows, at least 4096 elements each
-    i64 nseg = 1;
-    // (the sum-table fold of reduce_phase1 stages 64 KiB per workgroup: two workgroups per CU, long segments)
-    const bool tab_add = !is_mul && std::is_same<F, Lut>::value && sizeof(T) == 1 && fd.q <= 256 && fd.m > 1 && bt.add8;
-    const i64 want_blocks = (i64)num_cus() * (tab_add ? 2 : 8);
-    if (n_outer < want_blocks && len > 8192) {
-        nseg = std::min<i64>((want_blocks + n_outer - 1) / n_outer, (len + 4095) / 4096);
-        if (nseg > 4096) nseg = 4096;
-    }
-    if (nseg < 1) nseg = 1;
-    const i64 seg_len = len > 0 ? (len + nseg - 1) / nseg : 1;
-    int d = 0;
-    GFA_HIP(hipGetDevice(&d));
-    ReduceScratch &rs = g_reduce_scratch[d & 63];
-    const size_t need = (size_t)(n_outer * nseg);
-    if (rs.n < need) {
-        if (rs.p) (void)hipFree(rs.p);
-        rs.p = nullptr; rs.n = 0;
-        GFA_HIP(hipMalloc((void **)&rs.p, need * sizeof(u64)));
-        rs.n = need;
-    }
-    reduce_phase1<F, T>(fd, bt, is_mul, a, n_inner, col_begin, seg_len, nseg, n_outer, rs.p, st);
-    if (nseg > 8) { // few rows, many segments: a workgroup per row
-        if (is_mul)
-            hipLaunchKernelGGL((reduce_finalize_block_kernel<F, T, true>), dim3((unsigned)n_outer), dim3(256), 0, st, fd, (const T *)a, n_inner, rs.p, nseg, (T *)out, mode, err);
-        else
-            hipLaunchKernelGGL((reduce_finalize_block_kernel<F, T, false>), dim3((unsigned)n_outer), dim3(256), 0, st, fd, (const T *)a, n_inner, rs.p, nseg, (T *)out, mode, err);
-    } else if (is_mul)
-        hipLaunchKernelGGL((reduce_finalize_kernel<F, T, true>), dim3((unsigned)((n_outer + 255) / 256)), dim3(256), 0, st, fd, (const T *)a, n_inner, rs.p, nseg,
-                           (T *)out, n_outer, mode, err);
-    else
-        hipLaunchKernelGGL((reduce_finalize_kernel<F, T, false>), dim3((unsigned)((n_outer + 255) / 256)), dim3(256), 0, st, fd, (const T *)a, n_inner, rs.p, nseg,
-                           (T *)out, n_outer, mode, err);
-    GFA_HIP(hipGetLastError());
-    return GFA_OK;
-}
-
-int dispatch_reduce(const FieldDev &fd, const ByteTables &bt, int dtype, int op, const void *a, void *out, i64 n_outer, i64 n_inner,
-                    hipStream_t st, int32_t *err)
-{
-    GFA_DISPATCH_FT(launch_reduce_ft, fd, dtype, fd, bt, op, a, out, n_outer, n_inner, st, err);
-}
-
-
-// np.convolve(a, b) = polynomial product, direct form (convolve_jit.implementation, _domains/_function.py:141-167):
-// out[k] = sum_i a[i] * b[k - i].  One output coefficient per thread; large prime-field products go through the NTT
-// on the host side (galois_amd/_ntt.py) instead.
-template <class F, typename T>
-__global__ __launch_bounds__(256) void convolve_kernel(FieldDev fd, const T *__restrict__ a, i64 na, const T *__restrict__ b,
-                                                       i64 nb, T *__restrict__ out)
-{
-    typedef typename F::elem E;
-    const i64 n = na + nb - 1;
-    for (i64 k = (i64)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (i64)gridDim.x * blockDim.x) {
-        const i64 lo = k - (nb - 1) > 0 ? k - (nb - 1) : 0;
-        const i64 hi = k < na - 1 ? k : na - 1;
-        E acc = 0;
-        for (i64 i = lo; i <= hi; i++) acc = F::add(fd, acc, F::mul(fd, (E)a[i], (E)b[k - i]));
-        out[k] = (T)acc;
-    }
-}
-
-template <class F, typename T>
-int launch_convolve_ft(const FieldDev &fd, const void *a, i64 na, const void *b, i64 nb, void *out, hipStream_t st)
-{
-    const int grid = grid_for(na + nb - 1, 256, 8);
-    hipLaunchKernelGGL((convolve_kernel<F, T>), dim3(grid), dim3(256), 0, st, fd, (const T *)a, na, (const T *)b, nb, (T *)out);
-    GFA_HIP(hipGetLastError());
-    return GFA_OK;
-}
-
-int dispatch_convolve(const FieldDev &fd, int dtype, const void *a, i64 na, const void *b, i64 nb, void *out, hipStream_t st)
-{
-    GFA_DISPATCH_FT(launch_convolve_ft, fd, dtype, fd, a, na, b, nb, out, st);
-}
-
-
-// evaluate_elementwise_jit (_polys/_dense.py:432-440): y[i] = Horner(coeffs, x[i]), coefficients highest degree first.
-// The coefficient index is uniform across the wave, so the compiler keeps the coefficient stream in scalar loads.
-template <class F, typename T>
-__global__ __launch_bounds__(256) void poly_eval_kernel(FieldDev fd, const T *__restrict__ coeffs, i64 ncoef,
-                                                        const T *__restrict__ x, T *__restrict__ out, i64 n)
-{
-    typedef typename F::elem E;
-    for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (i64)gridDim.x * blockDim.x) {
-        const E xv = (E)x[i];
-        E acc = (E)coeffs[0];
-        for (i64 j = 1; j < ncoef; j++) acc = F::add(fd, F::mul(fd, acc, xv), (E)coeffs[j]);
-        out[i] = (T)acc;
-    }
-}
-
-template <class F, typename T>
-int launch_poly_eval_ft(const FieldDev &fd, const void *coeffs, i64 ncoef, const void *x, void *out, i64 n, hipStream_t st)
-{
-    const int grid = grid_for(n, 256, 8);
-    hipLaunchKernelGGL((poly_eval_kernel<F, T>), dim3(grid), dim3(256), 0, st, fd, (const T *)coeffs, ncoef, (const T *)x, (T *)out, n);
-    GFA_HIP(hipGetLastError());
-    return GFA_OK;
-}
-
-// r06: Horner's rule for the fields of at most 256 elements on uint8 arrays with the full 64 KiB PRODUCT table in LDS (row = the point x, fixed
-// per lane; column = the running value: random banks) -- one LDS gather per coefficient where the generic kernel does two or three gathers
-// from L2 (and two more through Zech logarithms per addition in odd characteristic; here the 64 KiB SUM table, row = the coefficient).
-// Four points per lane: four independent chains cover the gather latency.  One persistent 1024-thread workgroup per CU.
-template <bool ODD>
-__global__ __launch_bounds__(1024) void poly_eval_tab8_kernel(const uint8_t *__restrict__ mul8, const uint8_t *__restrict__ add8, const uint8_t *__restrict__ coeffs,
-                                                              i64 ncoef, const uint8_t *__restrict__ x, uint8_t *__restrict__ out, i64 n)
-{
-    extern __shared__ __attribute__((aligned(16))) uint8_t pe_lds[];
-    {
-        const uint4 *s0 = reinterpret_cast<const uint4 *>(mul8);
-        uint4 *d0 = reinterpret_cast<uint4 *>(pe_lds);
-        for (int i = threadIdx.x; i < 4096; i += 1024) d0[i] = s0[i];
-        if (ODD) {
-            const uint4 *s1 = reinterpret_cast<const uint4 *>(add8);
-            for (int i = threadIdx.x; i < 4096; i += 1024) d0[4096 + i] = s1[i];
-        }
-    }
-    __syncthreads();
-    const uint8_t *mt = pe_lds, *at = pe_lds + 65536;
-    const i64 stride = (i64)gridDim.x * 1024;
-    for (i64 i0 = (i64)blockIdx.x * 1024 + threadIdx.x; i0 < n; i0 += 4 * stride) {
-        u32 row[4], acc[4];
-        const u32 c0 = coeffs[0];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const i64 i = i0 + k * stride;
-            row[k] = (i < n ? (u32)x[i] : 0u) << 8;
-            acc[k] = c0;
-        }
-        for (i64 j = 1; j < ncoef; j++) {
-            const u32 c = coeffs[j]; // uniform: a scalar load
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const u32 prod = mt[row[k] | acc[k]];
-                acc[k] = ODD ? (u32)at[(c << 8) | prod] : (prod ^ c);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const i64 i = i0 + k * stride;
-            if (i < n) out[i] = (uint8_t)acc[k];
-        }
-    }
-}
-
-int launch_poly_eval_tab8(const uint8_t *mul8, const uint8_t *add8, bool odd, const void *coeffs, i64 ncoef, const void *x, void *out, i64 n, hipStream_t st)
-{
-    static bool attr[2] = {false, false};
-    const size_t lds = odd ? 131072 : 65536;
-    const void *k = odd ? (const void *)poly_eval_tab8_kernel<true> : (const void *)poly_eval_tab8_kernel<false>;
-    if (!attr[odd]) { GFA_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr[odd] = true; }
-    const i64 blocks = (n + 4095) / 4096;
-    const int grid = (int)std::min<i64>(blocks, (i64)num_cus());
-    if (odd)
-        hipLaunchKernelGGL(poly_eval_tab8_kernel<true>, dim3(grid), dim3(1024), lds, st, mul8, add8, (const uint8_t *)coeffs, ncoef, (const uint8_t *)x, (uint8_t *)out, n);
-    else
-        hipLaunchKernelGGL(poly_eval_tab8_kernel<false>, dim3(grid), dim3(1024), lds, st, mul8, add8, (const uint8_t *)coeffs, ncoef, (const uint8_t *)x, (uint8_t *)out, n);
-    GFA_HIP(hipGetLastError());
-    return GFA_OK;
-}
-
-int dispatch_poly_eval(const FieldDev &fd, int dtype, const void *coeffs, i64 ncoef, const void *x, void *out, i64 n, hipStream_t st)
-{
-    GFA_DISPATCH_FT(launch_poly_eval_ft, fd, dtype, fd, coeffs, ncoef, x, out, n, st);
-}
-
 // log_ufunc.lookup (_domains/_lookup.py:273-294): out[i] = LOG[a[i]] for base alpha.  For another primitive element
 // beta (stride-0 scalar or an array): log_beta(a) = LOG[a] * LOG[beta]^-1 mod (q - 1); a base that is not primitive has
 // no inverse exponent and is flagged (the reference's search raises ArithmeticError for it, _calculate.py:617).
@@ -1518,239 +977,6 @@ int launch_digits(u64 p, int m, const void *in, int dtype_in, void *out, int dty
     return GFA_OK;
 }
 
-// berlekamp_massey_jit.implementation (_lfsr.py:1647-1702): shortest LFSR (connection polynomial C, ascending) of each of
-// `batch` sequences of length n.  One 64-lane workgroup per sequence, C / B / T in LDS; the discrepancy is a strided
-// partial sum folded in LDS.  out_c: (batch, n) ascending coefficients, zero padded; out_len: trimmed length (>= 1).
-template <class F, typename T>
-__global__ __launch_bounds__(64) void berlekamp_massey_kernel(FieldDev fd, const T *__restrict__ seq, i64 n, T *__restrict__ out_c,
-                                                              i64 *__restrict__ out_len)
-{
-    typedef typename F::elem E;
-    extern __shared__ __attribute__((aligned(16))) unsigned char bm_raw[];
-    E *C = reinterpret_cast<E *>(bm_raw), *B = C + n, *Tm = B + n;
-    __shared__ u64 part[64];
-    const T *S = seq + (i64)blockIdx.x * n;
-    const int tid = threadIdx.x;
-    for (i64 i = tid; i < n; i += 64) { C[i] = i == 0 ? F::one(fd) : (E)0; B[i] = C[i]; }
-    __syncthreads();
-    i64 L = 0, m = 1;
-    E b = F::one(fd);
-    for (i64 k = 0; k < n; k++) {
-        E acc = 0;
-        for (i64 i = tid; i <= L; i += 64) acc = F::add(fd, acc, F::mul(fd, (E)S[k - i], C[i]));
-        part[tid] = (u64)acc;
-        __syncthreads();
-        for (int off = 32; off >= 1; off >>= 1) {
-            if (tid < off) part[tid] = (u64)F::add(fd, (E)part[tid], (E)part[tid + off]);
-            __syncthreads();
-        }
-        const E d = (E)part[0];
-        __syncthreads();
-        if (d == 0) { m++; continue; }
-        E coef;
-        if constexpr (std::is_same<F, Lut>::value) coef = Lut::div_nz(fd, d, b);
-        else coef = F::mul(fd, d, F::inv(fd, b));
-        const bool grow = !(2 * L > k);
-        if (grow) for (i64 i = tid; i < n; i += 64) Tm[i] = C[i];
-        __syncthreads();
-        for (i64 i = m + tid; i < n; i += 64) C[i] = F::sub(fd, C[i], F::mul(fd, coef, B[i - m]));
-        __syncthreads();
-        if (grow) {
-            for (i64 i = tid; i < n; i += 64) B[i] = Tm[i];
-            L = k + 1 - L; b = d; m = 1;
-        } else {
-            m++;
-        }
-        __syncthreads();
-    }
-    // C[: L + 1], trailing zeros trimmed (at least one coefficient)
-    const i64 clen = L + 1 < n ? L + 1 : n;
-    if (tid == 0) {
-        i64 last = 0;
-        for (i64 i = 0; i < clen; i++) if (C[i] != 0) last = i;
-        out_len[blockIdx.x] = last + 1;
-    }
-    for (i64 i = tid; i < n; i += 64) out_c[(i64)blockIdx.x * n + i] = i < clen ? (T)C[i] : (T)0;
-}
-
-template <class F, typename T>
-int launch_bm_ft(const FieldDev &fd, const void *seq, i64 n, i64 batch, void *out_c, i64 *out_len, hipStream_t st)
-{
-    typedef typename F::elem E;
-    const size_t lds = 3 * (size_t)n * sizeof(E);
-    auto k = berlekamp_massey_kernel<F, T>;
-    static bool attr = false;
-    if (!attr) { GFA_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)); attr = true; }
-    hipLaunchKernelGGL(k, dim3((unsigned)batch), dim3(64), lds, st, fd, (const T *)seq, n, (T *)out_c, out_len);
-    GFA_HIP(hipGetLastError());
-    return GFA_OK;
-}
-int dispatch_bm(const FieldDev &fd, int dtype, const void *seq, i64 n, i64 batch, void *out_c, i64 *out_len, hipStream_t st)
-{
-    GFA_DISPATCH_FT(launch_bm_ft, fd, dtype, fd, seq, n, batch, out_c, out_len, st);
-}
-
-// ufunc.accumulate over the last axis: one workgroup per row, 256-element chunks scanned in LDS with a running carry.
-// mode 0: inclusive scan with the op; 1: out[i] = a0 - (a1 + ... + ai); 2: out[i] = a0 / (a1 * ... * ai)
-// r06: a row may be cut into nseg segments of seg_len elements, one workgroup each, that start from carry_in[row * nseg + seg] -- the fold of
-// everything before the segment (accumulate_carries_kernel) -- so that ONE long row fills the chip; nseg = 1, carry_in = nullptr: the whole row.
-template <class F, typename T, bool IS_MUL>
-__global__ __launch_bounds__(256) void accumulate_kernel(FieldDev fd, const T *__restrict__ in, T *__restrict__ out, i64 n_inner,
-                                                         int mode, int32_t *err, i64 nseg, i64 seg_len, const u64 *__restrict__ carry_in)
-{
-    typedef typename F::elem E;
-    __shared__ u64 sh[256];
-    const i64 row = (i64)blockIdx.x / nseg, seg = (i64)blockIdx.x % nseg;
-    const T *x = in + row * n_inner;
-    T *y = out + row * n_inner;
-    const E ident = IS_MUL ? F::one(fd) : (E)0;
-    const E a0 = (E)x[0];
-    E carry = carry_in ? (E)carry_in[blockIdx.x] : ident;
-    bool bad = false;
-    const i64 start = (mode ? 1 : 0) + seg * seg_len;
-    i64 stop = nseg == 1 ? n_inner : start + seg_len;
-    if (stop > n_inner) stop = n_inner;
-    if (mode && seg == 0 && threadIdx.x == 0) y[0] = (T)a0;
-    constexpr int PER = 8; // consecutive elements per thread and iteration: one LDS scan (16 barriers) per 2048 elements instead of per 256
-    for (i64 base = start; base < stop; base += 256 * PER) {
-        const i64 i0 = base + (i64)threadIdx.x * PER;
-        E w[PER];
-        E v = ident; // running fold of this thread's elements
-#pragma unroll
-        for (int j = 0; j < PER; j++) {
-            const E e = i0 + j < stop ? (E)x[i0 + j] : ident;
-            v = IS_MUL ? F::mul(fd, v, e) : F::add(fd, v, e);
-            w[j] = v; // inclusive scan inside the thread
-        }
-        sh[threadIdx.x] = (u64)v;
-        __syncthreads();
-        for (int off = 1; off < 256; off <<= 1) {
-            E o = ident;
-            if ((int)threadIdx.x >= off) o = (E)sh[threadIdx.x - off];
-            __syncthreads();
-            if ((int)threadIdx.x >= off) {
-                v = IS_MUL ? F::mul(fd, o, v) : F::add(fd, o, v);
-                sh[threadIdx.x] = (u64)v;
-            }
-            __syncthreads();
-        }
-        const E before = threadIdx.x ? (E)sh[threadIdx.x - 1] : ident;               // the threads before this one, in this chunk
-        const E lead = IS_MUL ? F::mul(fd, carry, before) : F::add(fd, carry, before); // everything before this thread's elements
-        const E total = IS_MUL ? F::mul(fd, carry, (E)sh[255]) : F::add(fd, carry, (E)sh[255]);
-#pragma unroll
-        for (int j = 0; j < PER; j++) {
-            if (i0 + j < stop) {
-                const E r = IS_MUL ? F::mul(fd, lead, w[j]) : F::add(fd, lead, w[j]);
-                E o = r;
-                if (mode == 1) o = F::sub(fd, a0, r);
-                if (mode == 2) {
-                    if (r == 0) { bad = true; o = 0; }
-                    else if (a0 == 0) o = 0;
-                    else {
-                        if constexpr (std::is_same<F, Lut>::value) o = Lut::div_nz(fd, a0, r);
-                        else o = F::mul(fd, a0, F::inv(fd, r));
-                    }
-                }
-                y[i0 + j] = (T)o;
-            }
-        }
-        carry = total;
-        __syncthreads();
-    }
-    flag_error(err, bad);
-}
-
-// partial[row * nseg + seg] (the fold of segment seg) -> the fold of the segments before it.  One workgroup per row: every thread folds
-// its run of ceil(nseg / 256) partials, the 256 run totals are scanned in LDS, the runs are rewritten from their prefix
-template <class F, bool IS_MUL>
-__global__ __launch_bounds__(256) void accumulate_carries_kernel(FieldDev fd, u64 *__restrict__ partial, i64 nseg, i64 n_outer)
-{
-    typedef typename F::elem E;
-    __shared__ u64 sh[256];
-    const i64 row = blockIdx.x;
-    const E ident = IS_MUL ? F::one(fd) : (E)0;
-    const i64 c = (nseg + 255) / 256, lo = (i64)threadIdx.x * c;
-    i64 hi = lo + c;
-    if (hi > nseg) hi = nseg;
-    u64 *pr = partial + row * nseg;
-    E loc = ident;
-    for (i64 sg = lo; sg < hi; sg++) { const E v = (E)pr[sg]; loc = IS_MUL ? F::mul(fd, loc, v) : F::add(fd, loc, v); }
-    E v = loc;
-    sh[threadIdx.x] = (u64)v;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {
-        E o = ident;
-        if ((int)threadIdx.x >= off) o = (E)sh[threadIdx.x - off];
-        __syncthreads();
-        if ((int)threadIdx.x >= off) { v = IS_MUL ? F::mul(fd, o, v) : F::add(fd, o, v); sh[threadIdx.x] = (u64)v; }
-        __syncthreads();
-    }
-    E run = threadIdx.x ? (E)sh[threadIdx.x - 1] : ident; // the fold of every run before this one
-    for (i64 sg = lo; sg < hi; sg++) {
-        const E x = (E)pr[sg];
-        pr[sg] = (u64)run;
-        run = IS_MUL ? F::mul(fd, run, x) : F::add(fd, run, x);
-    }
-    (void)n_outer;
-}
-
-template <class F, typename T>
-int launch_accumulate_ft(const FieldDev &fd, const ByteTables &bt, int op, const void *a, void *out, i64 n_outer, i64 n_inner, hipStream_t st,
-                         int32_t *err)
-{
-    const int mode = op == GFA_OP_SUB ? 1 : op == GFA_OP_DIV ? 2 : 0;
-    const bool is_mul = op == GFA_OP_MUL || op == GFA_OP_DIV;
-    // r06: few long rows (np.cumsum of a 1-D array): segment folds -> carries -> segment scans, instead of one workgroup for the whole row
-    const i64 col_begin = mode ? 1 : 0, len = n_inner - col_begin;
-    const i64 want_blocks = (i64)num_cus() * 8;
-    if (n_outer < want_blocks / 4 && len >= ((i64)1 << 16)) {
-        i64 nseg = std::min<i64>((want_blocks + n_outer - 1) / n_outer, len / 8192);
-        if (nseg > 4096) nseg = 4096;
-        if (nseg >= 2) {
-            const i64 seg_len = ((len + nseg - 1) / nseg + 255) / 256 * 256;
-            nseg = (len + seg_len - 1) / seg_len;
-            int d = 0;
-            GFA_HIP(hipGetDevice(&d));
-            ReduceScratch &rs = g_reduce_scratch[d & 63];
-            const size_t need = (size_t)(n_outer * nseg);
-            if (rs.n < need) {
-                if (rs.p) (void)hipFree(rs.p);
-                rs.p = nullptr; rs.n = 0;
-                GFA_HIP(hipMalloc((void **)&rs.p, need * sizeof(u64)));
-                rs.n = need;
-            }
-            reduce_phase1<F, T>(fd, bt, is_mul, a, n_inner, col_begin, seg_len, nseg, n_outer, rs.p, st);
-            if (is_mul) {
-                hipLaunchKernelGGL((accumulate_carries_kernel<F, true>), dim3((unsigned)n_outer), dim3(256), 0, st, fd, rs.p, nseg, n_outer);
-                hipLaunchKernelGGL((accumulate_kernel<F, T, true>), dim3((unsigned)(n_outer * nseg)), dim3(256), 0, st, fd, (const T *)a, (T *)out, n_inner, mode, err, nseg,
-                                   seg_len, (const u64 *)rs.p);
-            } else {
-                hipLaunchKernelGGL((accumulate_carries_kernel<F, false>), dim3((unsigned)n_outer), dim3(256), 0, st, fd, rs.p, nseg, n_outer);
-                hipLaunchKernelGGL((accumulate_kernel<F, T, false>), dim3((unsigned)(n_outer * nseg)), dim3(256), 0, st, fd, (const T *)a, (T *)out, n_inner, mode, err, nseg,
-                                   seg_len, (const u64 *)rs.p);
-            }
-            GFA_HIP(hipGetLastError());
-            return GFA_OK;
-        }
-    }
-    if (is_mul)
-        hipLaunchKernelGGL((accumulate_kernel<F, T, true>), dim3((unsigned)n_outer), dim3(256), 0, st, fd, (const T *)a, (T *)out,
-                           n_inner, mode, err, (i64)1, (i64)0, (const u64 *)nullptr);
-    else
-        hipLaunchKernelGGL((accumulate_kernel<F, T, false>), dim3((unsigned)n_outer), dim3(256), 0, st, fd, (const T *)a, (T *)out,
-                           n_inner, mode, err, (i64)1, (i64)0, (const u64 *)nullptr);
-    GFA_HIP(hipGetLastError());
-    return GFA_OK;
-}
-
-int dispatch_accumulate(const FieldDev &fd, const ByteTables &bt, int dtype, int op, const void *a, void *out, i64 n_outer, i64 n_inner,
-                        hipStream_t st, int32_t *err)
-{
-    GFA_DISPATCH_FT(launch_accumulate_ft, fd, dtype, fd, bt, op, a, out, n_outer, n_inner, st, err);
-}
-
-
-
 int tab8_grid(i64 n)
 {
     i64 blocks = ((n >> 4) + TAB8_THREADS - 1) / TAB8_THREADS;
@@ -1812,10 +1038,7 @@ int launch_tab8_unary(const uint8_t *table256, bool check_zero, const void *a, v
         }
         return GFA_OK;
     }
-    i64 blocks = ((n >> 4) + TAB8_THREADS - 1) / TAB8_THREADS;
-    i64 cap = (i64)num_cus() * 2;
-    if (blocks < 1) blocks = 1;
-    const int grid = (int)(blocks < cap ? blocks : cap);
+    const int grid = tab8_grid(n);
     if (check_zero)
         hipLaunchKernelGGL((tab8_unary_kernel<true>), dim3(grid), dim3(TAB8_THREADS), 0, st, table256,
                            (const uint8_t *)a, (uint8_t *)out, n, err);
@@ -1829,10 +1052,7 @@ int launch_tab8_unary(const uint8_t *table256, bool check_zero, const void *a, v
 // x ** k on uint8 storage, one exponent for the whole array (device memory): tab8_unary_kernel<true, true>, one launch
 int launch_pow8(const FieldDev &lut, const void *a, const i64 *e, void *out, i64 n, hipStream_t st, int32_t *err)
 {
-    i64 blocks = ((n >> 4) + TAB8_THREADS - 1) / TAB8_THREADS;
-    const i64 cap = (i64)num_cus() * 2;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL((tab8_unary_kernel<true, true>), dim3((int)(blocks < cap ? blocks : cap)), dim3(TAB8_THREADS), 0, st,
+    hipLaunchKernelGGL((tab8_unary_kernel<true, true>), dim3(tab8_grid(n)), dim3(TAB8_THREADS), 0, st,
                        (const uint8_t *)nullptr, (const uint8_t *)a, (uint8_t *)out, n, err, lut, e);
     GFA_HIP(hipGetLastError());
     return GFA_OK;
@@ -2128,86 +1348,6 @@ int gfa_scalar_multiply(gfa_field_t *f, const void *a, int64_t sa, const int64_t
     return dispatch_intarg(f->calc, dtype, false, a, sa, ks, sk, out, n, (hipStream_t)stream, nullptr);
 }
 
-int gfa_reduce(gfa_field_t *f, int op, const void *a, void *out, int64_t n_outer, int64_t n_inner, int dtype,
-               gfa_stream_t stream, int32_t *dev_err)
-{
-    if (!f || !a || !out || n_outer < 0 || n_inner < 1 || op < GFA_OP_ADD || op > GFA_OP_DIV) {
-        set_error("gfa_reduce: bad arguments");
-        return GFA_ERR_INVALID;
-    }
-    if (!dtype_holds(dtype, f->calc.q)) { set_error("dtype cannot hold the field's elements"); return GFA_ERR_INVALID; }
-    if (n_outer == 0) return GFA_OK;
-    FieldDeviceState *ds;
-    int rc = f->ensure_device(nullptr, &ds);
-    if (rc) return rc;
-    ByteTables bt;
-    bt.log8 = ds->log8; bt.exp8 = ds->exp8; bt.add8 = ds->add8;
-    if (f->use_lookup()) return dispatch_reduce(f->lut_desc(*ds), bt, dtype, op, a, out, n_outer, n_inner, (hipStream_t)stream, dev_err);
-    return dispatch_reduce(f->calc, bt, dtype, op, a, out, n_outer, n_inner, (hipStream_t)stream, dev_err);
-}
-
-int gfa_reduceat(gfa_field_t *f, int op, const void *a, const int64_t *starts, const int64_t *ends, int64_t nseg, void *out, int dtype,
-                 gfa_stream_t stream, int32_t *dev_err)
-{
-    if (!f || nseg < 0 || op < GFA_OP_ADD || op > GFA_OP_DIV) { set_error("gfa_reduceat: bad arguments"); return GFA_ERR_INVALID; }
-    if (!dtype_holds(dtype, f->calc.q)) { set_error("dtype cannot hold the field's elements"); return GFA_ERR_INVALID; }
-    if (nseg == 0) return GFA_OK;
-    if (!a || !starts || !ends || !out || nseg > 0x7fffffff) { set_error("gfa_reduceat: bad arguments"); return GFA_ERR_INVALID; }
-    FieldDeviceState *ds;
-    int rc = f->ensure_device(nullptr, &ds);
-    if (rc) return rc;
-    if (f->use_lookup())
-        return dispatch_reduceat(f->lut_desc(*ds), dtype, op, a, (const i64 *)starts, (const i64 *)ends, nseg, out, (hipStream_t)stream, dev_err);
-    return dispatch_reduceat(f->calc, dtype, op, a, (const i64 *)starts, (const i64 *)ends, nseg, out, (hipStream_t)stream, dev_err);
-}
-
-int gfa_accumulate(gfa_field_t *f, int op, const void *a, void *out, int64_t n_outer, int64_t n_inner, int dtype,
-                   gfa_stream_t stream, int32_t *dev_err)
-{
-    if (!f || n_outer < 0 || n_inner < 0 || op < GFA_OP_ADD || op > GFA_OP_DIV) {
-        set_error("gfa_accumulate: bad arguments");
-        return GFA_ERR_INVALID;
-    }
-    if (n_outer == 0 || n_inner == 0) return GFA_OK;
-    if (!a || !out) { set_error("gfa_accumulate: bad arguments"); return GFA_ERR_INVALID; }
-    if (!dtype_holds(dtype, f->calc.q)) { set_error("dtype cannot hold the field's elements"); return GFA_ERR_INVALID; }
-    FieldDeviceState *ds;
-    int rc = f->ensure_device(nullptr, &ds);
-    if (rc) return rc;
-    ByteTables bt;
-    bt.log8 = ds->log8; bt.exp8 = ds->exp8; bt.add8 = ds->add8;
-    if (f->use_lookup()) return dispatch_accumulate(f->lut_desc(*ds), bt, dtype, op, a, out, n_outer, n_inner, (hipStream_t)stream, dev_err);
-    return dispatch_accumulate(f->calc, bt, dtype, op, a, out, n_outer, n_inner, (hipStream_t)stream, dev_err);
-}
-
-int gfa_convolve(gfa_field_t *f, const void *a, int64_t na, const void *b, int64_t nb, void *out, int dtype,
-                 gfa_stream_t stream)
-{
-    if (!f || !a || !b || !out || na < 1 || nb < 1) { set_error("gfa_convolve: bad arguments"); return GFA_ERR_INVALID; }
-    if (!dtype_holds(dtype, f->calc.q)) { set_error("dtype cannot hold the field's elements"); return GFA_ERR_INVALID; }
-    FieldDeviceState *ds;
-    int rc = f->ensure_device(nullptr, &ds);
-    if (rc) return rc;
-    if (convolve_crt_eligible(f->calc, na, nb)) return convolve_crt(f, dtype, a, na, b, nb, out, (hipStream_t)stream);
-    if (f->use_lookup()) return dispatch_convolve(f->lut_desc(*ds), dtype, a, na, b, nb, out, (hipStream_t)stream);
-    return dispatch_convolve(f->calc, dtype, a, na, b, nb, out, (hipStream_t)stream);
-}
-
-int gfa_berlekamp_massey(gfa_field_t *f, const void *seq, int64_t n, int64_t batch, void *out_coeffs, int64_t *out_len, int dtype,
-                          gfa_stream_t stream)
-{
-    if (!f || n < 1 || batch < 0) { set_error("gfa_berlekamp_massey: bad arguments"); return GFA_ERR_INVALID; }
-    if (!dtype_holds(dtype, f->calc.q)) { set_error("dtype cannot hold the field's elements"); return GFA_ERR_INVALID; }
-    if (batch == 0) return GFA_OK;
-    if (!seq || !out_coeffs || !out_len) { set_error("gfa_berlekamp_massey: bad arguments"); return GFA_ERR_INVALID; }
-    if (n > 6000 || batch > 0x7fffffff) { set_error("gfa_berlekamp_massey: sequences are limited to 6000 terms"); return GFA_ERR_UNSUPPORTED; }
-    FieldDeviceState *ds;
-    int rc = f->ensure_device(nullptr, &ds);
-    if (rc) return rc;
-    if (f->use_lookup()) return dispatch_bm(f->lut_desc(*ds), dtype, seq, n, batch, out_coeffs, (i64 *)out_len, (hipStream_t)stream);
-    return dispatch_bm(f->calc, dtype, seq, n, batch, out_coeffs, (i64 *)out_len, (hipStream_t)stream);
-}
-
 int gfa_vector(gfa_field_t *f, int to_digits, const void *in, int dtype_in, void *out, int dtype_out, int64_t n, gfa_stream_t stream)
 {
     if (!f || n < 0 || dtype_in < GFA_U8 || dtype_in > GFA_U64 || dtype_out < GFA_U8 || dtype_out > GFA_U64) {
@@ -2222,22 +1362,6 @@ int gfa_vector(gfa_field_t *f, int to_digits, const void *in, int dtype_in, void
     if (!in || !out) { set_error("gfa_vector: bad arguments"); return GFA_ERR_INVALID; }
     if (to_digits) return launch_digits<true>(f->calc.p, (int)f->calc.m, in, dtype_in, out, dtype_out, n, (hipStream_t)stream);
     return launch_digits<false>(f->calc.p, (int)f->calc.m, in, dtype_in, out, dtype_out, n, (hipStream_t)stream);
-}
-
-int gfa_poly_evaluate(gfa_field_t *f, const void *coeffs, int64_t ncoef, const void *x, void *out, int64_t n, int dtype,
-                      gfa_stream_t stream)
-{
-    if (!f || !coeffs || ncoef < 1 || n < 0) { set_error("gfa_poly_evaluate: bad arguments"); return GFA_ERR_INVALID; }
-    if (!dtype_holds(dtype, f->calc.q)) { set_error("dtype cannot hold the field's elements"); return GFA_ERR_INVALID; }
-    if (n == 0) return GFA_OK;
-    if (!x || !out) { set_error("gfa_poly_evaluate: bad arguments"); return GFA_ERR_INVALID; }
-    FieldDeviceState *ds;
-    int rc = f->ensure_device(nullptr, &ds);
-    if (rc) return rc;
-    if (f->has_tab8 && f->use_lookup() && dtype == GFA_U8 && ds->mul8 && (f->calc.p == 2 || ds->add8) && n >= 65536 && ncoef >= 4) // r06: product (and sum) table in LDS
-        return launch_poly_eval_tab8(ds->mul8, ds->add8, f->calc.p != 2, coeffs, ncoef, x, out, n, (hipStream_t)stream);
-    if (f->use_lookup()) return dispatch_poly_eval(f->lut_desc(*ds), dtype, coeffs, ncoef, x, out, n, (hipStream_t)stream);
-    return dispatch_poly_eval(f->calc, dtype, coeffs, ncoef, x, out, n, (hipStream_t)stream);
 }
 
 int gfa_log(gfa_field_t *f, const void *a, int64_t a_stride, const void *base, int64_t base_stride, int64_t *out, int64_t n,

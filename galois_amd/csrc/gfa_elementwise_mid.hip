@@ -509,18 +509,6 @@ __global__ __launch_bounds__(THREADS) void big16_addsub_kernel(MidDesc d, const 
     }
 }
 
-int mid_num_cus()
-{
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-        if (cus <= 0) cus = 256;
-    }
-    return cus;
-}
-
 template <int OP, int ESZ>
 int mid_launch_e(const MidDesc &d, const void *a, i64 sa, const void *b, i64 sb, void *out, i64 n, hipStream_t st, int32_t *err)
 {
@@ -530,7 +518,7 @@ int mid_launch_e(const MidDesc &d, const void *a, i64 sa, const void *b, i64 sb,
     const size_t lds = ((size_t)d.qa + d.exp_len + (NEED_ZECH ? d.qa : 0)) * sizeof(u16);
     const bool reduced = d.exp_len == d.qa;
     static bool attr[2] = {false, false};
-    const int cus = mid_num_cus();
+    const int cus = num_cus();
     const i64 vec_blocks = (n >> LOGV);
     if (reduced) { // 8192 < q <= 32768: up to 160 KiB of tables, one 16-wave workgroup per CU
         auto k = mid_kernel<OP, 1024, true, ESZ>;
@@ -749,7 +737,7 @@ int big16_inv_launch(const MidDesc &d, const FieldDev &lut, const void *a, i64 s
     const size_t lds = (size_t)d.qa * sizeof(u16) + (MODE == 2 ? 1024 : 0);
     const i64 nvec = n >> 3;
     const i64 blocks = (nvec + T - 1) / T;
-    const int cus = mid_num_cus();
+    const int cus = num_cus();
     if (MODE == 3) { // the per-call power table: qa entries of stream-ordered scratch
         u16 *tab = nullptr;
         if (gfa::scratch_alloc((void **)&tab, (size_t)d.qa * sizeof(u16), st) != hipSuccess) { (void)hipGetLastError(); return GFA_ERR_UNSUPPORTED; }
@@ -817,7 +805,7 @@ int big16_launch(const MidDesc &d, const void *a, i64 sa, const void *b, i64 sb,
 {
     const size_t lds = (size_t)d.qa * sizeof(u16);
     const i64 nvec = n >> 3;
-    const int cus = mid_num_cus();
+    const int cus = num_cus();
     // JB vectors per lane (tiles of 4096 * JB elements) when that
     // still gives every CU two tiles, else two vectors per lane
     constexpr int JB = ((OP == GFA_OP_MUL || OP == GFA_OP_DIV) ? 4 : 8) * 512 / B16_THREADS; // two operand streams: half the vectors per lane (registers)
@@ -875,7 +863,7 @@ int big16_addsub_launch(const MidDesc &d, const void *a, i64 sa, const void *b, 
     constexpr int T = 1024; // 16 waves: the three phases are latency chains (gather, barrier, stage, barrier)
     const size_t lds = (size_t)d.qa * sizeof(u16);
     const i64 nvec = n >> 3;
-    const int cus = mid_num_cus();
+    const int cus = num_cus();
     static bool attr = false;
     auto k = big16_addsub_kernel<OP, 2, T>;
     if (!attr) { GFA_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, 131072)); attr = true; }
@@ -959,14 +947,14 @@ int mid_power_each(const FieldDev &lut, const void *image, const void *a, const 
         auto k = mid_powv_kernel<1024>;
         if (!attr) { GFA_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, 163840)); attr = true; }
         i64 blocks = ((n >> 3) + 1023) / 1024;
-        const i64 cap = mid_num_cus();
+        const i64 cap = num_cus();
         if (blocks < 1) blocks = 1;
         hipLaunchKernelGGL(k, dim3((int)(blocks < cap ? blocks : cap)), dim3(1024), lds, st, d, (const u16 *)a, e, (u16 *)out, n, err);
     } else {
         i64 per_cu = (i64)(160 * 1024) / (i64)(lds + 1024);
         per_cu = per_cu < 1 ? 1 : per_cu > 4 ? 4 : per_cu;
         i64 blocks = ((n >> 3) + MID_THREADS - 1) / MID_THREADS;
-        const i64 cap = (i64)mid_num_cus() * per_cu;
+        const i64 cap = (i64)num_cus() * per_cu;
         if (blocks < 1) blocks = 1;
         hipLaunchKernelGGL(mid_powv_kernel<MID_THREADS>, dim3((int)(blocks < cap ? blocks : cap)), dim3(MID_THREADS), lds, st, d, (const u16 *)a, e,
                            (u16 *)out, n, err);
@@ -1027,7 +1015,7 @@ int big16_power_each(const FieldDev &lut, const void *image, const void *a, cons
     }
     const size_t lds = (size_t)d.qa * sizeof(u16);
     const i64 nvec = n >> 3;
-    const int cus = mid_num_cus();
+    const int cus = num_cus();
     const i64 slice = std::min<i64>(nvec, (i64)1 << 23); // index slices of at most 128 MiB: they stay in the Infinity Cache between the two kernels
     u16 *idx = nullptr;
     if (gfa::scratch_alloc((void **)&idx, (size_t)slice * 16, st) != hipSuccess) { (void)hipGetLastError(); return GFA_ERR_UNSUPPORTED; }

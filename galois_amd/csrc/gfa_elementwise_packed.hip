@@ -379,12 +379,6 @@ int get_dev2(const FieldDev &c, Packed2Dev *out)
     return GFA_OK;
 }
 
-int num_cus()
-{
-    static const int cus = [] { int dev = 0, n = 0; return (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256; }();
-    return cus;
-}
-
 template <typename T, int OP>
 int launch(const PackedDev &d, const void *a, i64 sa, const void *b, i64 sb, void *out, i64 n, hipStream_t st)
 {

@@ -62,6 +62,19 @@ hipError_t scratch_alloc(void **p, size_t bytes, hipStream_t st)
 
 hipError_t scratch_free(void *p, hipStream_t st) { return hipFreeAsync(p, st); }
 
+int num_cus()
+{
+    static int cached[64] = {0};
+    int d = 0;
+    if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) return 256;
+    if (!cached[d]) {
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, d) != hipSuccess) return 256;
+        cached[d] = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    }
+    return cached[d];
+}
+
 // returns the pool's unused blocks beyond `keep_bytes` to the driver (current device); GFA_OK when no pool exists yet
 int scratch_trim(size_t keep_bytes)
 {

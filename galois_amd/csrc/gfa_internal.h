@@ -1,4 +1,4 @@
-// gfa_internal.h -- host-side objects behind the opaque C-ABI handles.
+// gfa_internal.h -- host-side objects behind the opaque C-ABI handles, and the launch / device helpers the kernel files share.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -33,6 +33,51 @@ int time_loop(hipStream_t st, int iters, float *ms_out, const std::function<int(
 hipError_t scratch_alloc(void **p, size_t bytes, hipStream_t st);
 hipError_t scratch_free(void *p, hipStream_t st);
 int scratch_trim(size_t keep_bytes); // synchronises the device, returns unused pool memory beyond keep_bytes to the driver
+
+// compute units of the current device, cached per device (256 when the query fails)
+int num_cus();
+
+inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+inline int grid_for(i64 work_items, int threads, int blocks_per_cu)
+{
+    i64 blocks = (work_items + threads - 1) / threads;
+    i64 cap = (i64)num_cus() * blocks_per_cu;
+    if (blocks < 1) blocks = 1;
+    return (int)(blocks < cap ? blocks : cap);
+}
+
+// Streaming kernels without per-workgroup set-up are launched FLAT (one 16-byte vector per thread).  With a persistent
+// grid-stride launch the workgroups drift apart, the active address window spreads and HBM efficiency drops once the
+// arrays exceed the Infinity Cache: 5.0 vs 6.0-6.6 TB/s on 1e9-byte operands (tools/ubench/stream_big.hip).
+inline int grid_flat(i64 work_items, int threads)
+{
+    i64 blocks = (work_items + threads - 1) / threads;
+    if (blocks < 1) blocks = 1;
+    return (int)(blocks < 0x7fffffff ? blocks : 0x7fffffff);
+}
+
+__device__ __forceinline__ void flag_error(int32_t *err, bool bad)
+{
+    // one atomic per wave at most
+    if (__any(bad)) {
+        if ((threadIdx.x & 63) == 0 && err) atomicOr(err, GFA_DEVERR_ZERO_DIVISION);
+    }
+}
+
+template <class F, int OP>
+__device__ __forceinline__ typename F::elem apply_binary(const FieldDev &fd, typename F::elem x, typename F::elem y, bool &bad)
+{
+    if constexpr (OP == GFA_OP_ADD) return F::add(fd, x, y);
+    else if constexpr (OP == GFA_OP_SUB) return F::sub(fd, x, y);
+    else if constexpr (OP == GFA_OP_MUL) return F::mul(fd, x, y);
+    else { // DIV: reciprocal of the divisor then multiply (divide_ufunc.__call__, _ufunc.py:433-437)
+        if (y == 0) { bad = true; return 0; }
+        if (x == 0) return 0;
+        if constexpr (std::is_same<F, Lut>::value) return Lut::div_nz(fd, x, y);
+        else return F::mul(fd, x, F::inv(fd, y));
+    }
+}
 
 void ntt_forget_field(const struct ::gfa_field *f); // drops cached NTT plans of a field being destroyed
 

@@ -825,13 +825,12 @@ int launch_one_t(const i32 *in, i32 *out, const M32OneArgs &oa, i64 batch, const
         attr = true;
     }
     // persistent: as many workgroups as fit the chip at once (LDS-limited), each looping over transforms with the next one's loads in flight
-    static const int cus = [] { int dev = 0, n = 0; return (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256; }();
     // measured: persistence + prefetch gains 14 % at 2^15 points (one workgroup per CU: nothing else overlaps its load phase) and
     // nothing or a loss below (2^14: 0.150 -> 0.163 ms), where two or three workgroups per CU overlap each other
     const bool persist = LOGR0 == 5;
     const i64 nblk = (batch + G - 1) / G;
     const i64 per_cu = std::max<i64>(1, (i64)(160 * 1024) / (i64)lds);
-    const i64 grid = persist ? std::min<i64>(nblk, (i64)cus * per_cu) : nblk;
+    const i64 grid = persist ? std::min<i64>(nblk, (i64)num_cus() * per_cu) : nblk;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(G * 32 * R0), lds, st, in, out, oa, pl->one_net0, pl->one_net1, pl->one_mid, pl->one_wj, batch);
     GFA_HIP(hipGetLastError());
     return GFA_OK;
@@ -846,8 +845,7 @@ int launch_2e16_b(const i32 *in, i32 *out, const M32OneArgs &oa, i64 batch, cons
         GFA_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr = true;
     }
-    static const int cus = [] { int dev = 0, n = 0; return (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256; }();
-    const i64 grid = std::min<i64>(batch, cus); // persistent: one workgroup per CU (LDS-limited)
+    const i64 grid = std::min<i64>(batch, num_cus()); // persistent: one workgroup per CU (LDS-limited)
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(1024), B16_LDS_BYTES, st, in, out, oa, pl->one_net0, pl->one_net1, pl->one_mid, pl->one_wj, batch);
     GFA_HIP(hipGetLastError());
     return GFA_OK;

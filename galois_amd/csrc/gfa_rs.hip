@@ -1534,20 +1534,6 @@ int set_lds_limit(K kern, bool *done)
     return GFA_OK;
 }
 
-int cu_count()
-{ // cached per device: the property query is far slower than a kernel launch
-    static int cached[64] = {0};
-    int d = 0;
-    if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) return 256;
-    if (!cached[d]) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, d) != hipSuccess) return 256;
-        cached[d] = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
-    return cached[d];
-}
-
-
 template <bool DIV>
 int launch_poly(gfa_rs *code, const void *in, int len_in, void *out, i64 batch, hipStream_t st)
 { // DIV = false: polymul (len_in = ks); DIV = true: polydiv (len_in = ns)
@@ -1561,7 +1547,7 @@ int launch_poly(gfa_rs *code, const void *in, int len_in, void *out, i64 batch, 
     const int nk = rp.n - rp.k;
     const int nwaves = bin ? 16 : 8;
     const size_t lds = (bin ? 65536 : 131072) + 1280 + ((nk + 1 + 15) / 16) * 16 + (size_t)nwaves * 256;
-    const int grid = (int)std::max<i64>(1, std::min<i64>((batch + nwaves - 1) / nwaves, (i64)cu_count()));
+    const int grid = (int)std::max<i64>(1, std::min<i64>((batch + nwaves - 1) / nwaves, (i64)num_cus()));
     static bool a[2] = {false, false};
     if (bin) {
         auto k = DIV ? rs_polydiv_kernel<true> : rs_polymul_kernel<true>;
@@ -1595,8 +1581,8 @@ int launch_lfsr(gfa_rs *code, gfa_rs::Dev *cd, const uint8_t *in, const uint8_t 
         // 2^20), the decoder's pre-pass only from 2^19 (782 vs 688 GB/s of clean words at 2^20; 498 vs 562 at 2^17)
         const bool shape = nkw == 8 && !eras && ((ENCODE && len == 223 && batch >= ((i64)1 << 16)) || (!ENCODE && len == 255 && rem_out && batch >= ((i64)1 << 19)));
         if (shape) {
-            const int threads = batch >= (i64)1024 * cu_count() ? 1024 : 512; // one workgroup per CU (LDS); smaller ones cover every CU sooner
-            const int grid = (int)std::max<i64>(1, std::min<i64>((batch + threads - 1) / threads, (i64)cu_count()));
+            const int threads = batch >= (i64)1024 * num_cus() ? 1024 : 512; // one workgroup per CU (LDS); smaller ones cover every CU sooner
+            const int grid = (int)std::max<i64>(1, std::min<i64>((batch + threads - 1) / threads, (i64)num_cus()));
 #define GFA_LFSR_REG(LENV, MODEV)                                                                                        \
     do {                                                                                                                \
         static bool attr = false;                                                                                       \
@@ -1618,11 +1604,11 @@ int launch_lfsr(gfa_rs *code, gfa_rs::Dev *cd, const uint8_t *in, const uint8_t 
     static const int rep_env = [] { const char *e = getenv("GFA_RS_LFSR_REP4"); return e ? atoi(e) : 1; }();
     constexpr int kshift = 1; // which lanes share a table copy: pairs (measured against 0 and 2)
     const bool rep4 = rep_env && (nkw == 4 || nkw == 8) && (size_t)(nkw / 4) * 16384 + 8 * (size_t)stage_bytes <= 160 * 1024 &&
-                      (batch >= 64 * 8 * (i64)cu_count() / 2 || rep_env == 2); // smaller batches: more, smaller workgroups (2: always)
+                      (batch >= 64 * 8 * (i64)num_cus() / 2 || rep_env == 2); // smaller batches: more, smaller workgroups (2: always)
     const int threads = rep4 ? 512 : 256;
     const size_t lds = (rep4 ? (size_t)(nkw / 4) * 16384 : (size_t)256 * nk) + (size_t)(threads / 64) * stage_bytes;
     const i64 blocks = (batch + threads - 1) / threads;
-    const int grid = (int)std::max<i64>(1, std::min<i64>(blocks, (i64)cu_count() * (rep4 ? 1 : 2)));
+    const int grid = (int)std::max<i64>(1, std::min<i64>(blocks, (i64)num_cus() * (rep4 ? 1 : 2)));
 #define GFA_LFSR(W)                                                                                                     \
     case W: {                                                                                                           \
         static bool attr = false;                                                                                       \
@@ -1871,7 +1857,7 @@ int gfa_rs_encode(gfa_rs_t *code, const void *msg, int64_t ks, void *out, int64_
     if (lds > 160 * 1024) { set_error("gfa_rs_encode: code too large for the LDS-resident encoder"); return GFA_ERR_UNSUPPORTED; }
     const int threads = nwaves * 64;
     const i64 cw_per_block = (i64)nwaves * groups;
-    const int grid = (int)std::min<i64>((batch + cw_per_block - 1) / cw_per_block, (i64)cu_count());
+    const int grid = (int)std::min<i64>((batch + cw_per_block - 1) / cw_per_block, (i64)num_cus());
     static bool a0 = false, a1 = false;
     if (bin) {
         if ((rc = set_lds_limit(rs_encode_kernel<true>, &a0))) return rc;
@@ -1904,7 +1890,7 @@ static int launch_decode(gfa_rs_t *code, const void *recv, const uint8_t *erasur
     if (fixed + nwaves * per_wave > 160 * 1024) { set_error("gfa_rs_decode: code too large for LDS"); return GFA_ERR_UNSUPPORTED; }
     const size_t lds = fixed + ((nwaves * per_wave + 15) & ~(size_t)15) + 16;
     const int threads = nwaves * 64;
-    const int grid = (int)std::min<i64>((batch + nwaves - 1) / nwaves, (i64)cu_count());
+    const int grid = (int)std::min<i64>((batch + nwaves - 1) / nwaves, (i64)num_cus());
     static bool a[4] = {false, false, false, false};
 #define GFA_RS_LAUNCH(BINV, DET, IDX)                                                                                  \
     do {                                                                                                               \
@@ -2001,7 +1987,7 @@ int gfa_rs_decode(gfa_rs_t *code, const void *recv, const uint8_t *erasures, int
             const int nwaves = 2 * wps;
             const size_t lds = fixed + ((nwaves * per_wave + 15) & ~(size_t)15) + 16;
             const int per_cu = lds * 2 <= 160 * 1024 ? 2 : 1;
-            const int grid = (int)std::max<i64>(1, std::min<i64>((batch + nwaves - 1) / nwaves, (i64)cu_count() * per_cu));
+            const int grid = (int)std::max<i64>(1, std::min<i64>((batch + nwaves - 1) / nwaves, (i64)num_cus() * per_cu));
             RsParams rpk = rp;
             rpk.per_block = (int)((batch + grid - 1) / grid);
 #define GFA_K2(SV, W, IDX)                                                                                              \
@@ -2130,7 +2116,7 @@ int gfa_debug_rs_bm_selftest(gfa_field_t *f, int64_t nseq, uint64_t seed, int64_
     static bool attr = false;
     if ((rc = decode_lds_base_is_zero(rs_bm_selftest_kernel))) return rc;
     if ((rc = set_lds_limit(rs_bm_selftest_kernel, &attr))) return rc;
-    const int grid = (int)std::max<i64>(1, std::min<i64>((nseq + 3) / 4, 4 * (i64)cu_count()));
+    const int grid = (int)std::max<i64>(1, std::min<i64>((nseq + 3) / 4, 4 * (i64)num_cus()));
     hipLaunchKernelGGL(rs_bm_selftest_kernel, dim3(grid), dim3(256), 65536 + 16, st, ds->mul8, d_seq, d_len, d_out, (i64)nseq);
     GFA_HIP(hipGetLastError());
     std::vector<int> out((size_t)nseq);

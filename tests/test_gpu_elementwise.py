@@ -1532,6 +1532,47 @@ def test_folds_and_scans_of_long_one_dimensional_arrays(order):
         np.true_divide.accumulate(x)
 
 
+def test_folds_and_scans_of_long_rows_on_two_streams_at_once():
+    """gfa_reduce (add, multiply) and gfa_accumulate (add) over single rows of 2^24 GF(7340033) elements, enqueued on two streams with no
+    synchronisation between them: every call cuts its row into segments and keeps the segment folds in a work buffer of its own, so
+    concurrent callers on one device do not see each other's partials.  Every result against host arithmetic."""
+    import torch
+    from galois_amd import _lib as L
+
+    p = 7340033
+    GF = ga.GF(p)
+    n = (1 << 24) + 5
+    rng = np.random.default_rng(24)
+    rows = [rng.integers(1, p, n, dtype=np.uint64) for _ in range(4)]  # rows 0, 2 on the first stream, 1, 3 on the second
+    dev = [torch.from_numpy(r.astype(np.uint32).view(np.int32)).cuda() for r in rows]
+    sums = [torch.empty(1, dtype=torch.int32, device="cuda") for _ in rows]
+    prods = [torch.empty(1, dtype=torch.int32, device="cuda") for _ in rows]
+    scans = [torch.empty_like(d) for d in dev]
+    lib = L.lib()
+    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+    for s in streams:
+        s.wait_stream(torch.cuda.current_stream())  # the uploads, not each other
+    for i in range(len(rows)):
+        st = streams[i % 2].cuda_stream
+        L.check(lib.gfa_reduce(GF._handle, L.OP_ADD, dev[i].data_ptr(), sums[i].data_ptr(), 1, n, L.U32, st, None))
+        L.check(lib.gfa_reduce(GF._handle, L.OP_MUL, dev[i].data_ptr(), prods[i].data_ptr(), 1, n, L.U32, st, None))
+        L.check(lib.gfa_accumulate(GF._handle, L.OP_ADD, dev[i].data_ptr(), scans[i].data_ptr(), 1, n, L.U32, st, None))
+    torch.cuda.synchronize()
+
+    def product(v):
+        while len(v) > 1:
+            if len(v) & 1:
+                v = np.concatenate([v[:1] * v[-1:] % p, v[1:-1]])
+            v = v[: len(v) // 2] * v[len(v) // 2:] % p
+        return int(v[0])
+
+    u32 = lambda t: t.cpu().numpy().view(np.uint32).astype(np.uint64)
+    for i, r in enumerate(rows):
+        assert int(u32(sums[i])[0]) == int(r.sum() % p), (i, "add.reduce")
+        assert int(u32(prods[i])[0]) == product(r), (i, "multiply.reduce")
+        assert np.array_equal(u32(scans[i]), np.cumsum(r) % p), (i, "add.accumulate")
+
+
 @pytest.mark.parametrize("order", [2**8, 2**4, 2**16, 2**20, 2**32, 3**5, 7**3, 3**2, 5**4, 3**10, 31**2])
 def test_long_polynomial_products_over_extension_fields(order):
     """r06: np.convolve over GF(2^m) / GF(p^m) from 2^20 coefficient products: Karatsuba over the bit / digit positions, every leaf an exact
