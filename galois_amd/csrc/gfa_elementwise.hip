@@ -406,7 +406,14 @@ __device__ __forceinline__ u32 lookup4(const uint8_t *lds, u32 aw, u32 bw)
 // overlaps the first HBM round trip), and each lane re-arms its load for the next vector before it does the 16 LDS
 // lookups of the current one.  Measured (tools/ubench/stream3.hip, 1e8 elements): 46.9 us against 49.6 us for the
 // load-all / lookup-all / store-all loop; the plain a^b stream in the same launch shape takes 46.5 us.
-template <bool CHECK_ZERO_B>
+// NT_STORE: results leave through non-temporal stores (the loads stay ordinary).  r07, tools/ubench/stream4.hip at 1e8 elements,
+// variants interleaved, medians of 7 x 100 launches in two passes (profiles/r07_stream_order_1e8.txt): this kernel 46.6 / 46.4 us,
+// with non-temporal stores 44.1 / 43.8 us, with non-temporal loads 48.5 / 47.9, with both 49.0 / 48.9; the flat a^b launch
+// 46.8 / 48.7 (its best pass 43.9 / 43.6).  Every order in which workgroups CLAIM blocks lost at this size (51.3 .. 87 us): the
+// order was not what separated this kernel from the flat launch, the output lines allocated in the caches were.  The launch
+// chooses NT_STORE by array size, see launch_tab8_binary.  The flat launch is bimodal (passes at 43.6 .. 43.9 and at 46.8 .. 48.8);
+// against its MEDIAN this kernel had no gap left to close, against its best pass the non-temporal stores close 92 % of it.
+template <bool CHECK_ZERO_B, bool NT_STORE>
 __global__ __launch_bounds__(TAB8_THREADS) void tab8_binary_kernel(const uint8_t *__restrict__ table,
                                                                     const uint8_t *__restrict__ a,
                                                                     const uint8_t *__restrict__ b,
@@ -443,7 +450,8 @@ __global__ __launch_bounds__(TAB8_THREADS) void tab8_binary_kernel(const uint8_t
                     ((cy.w - 0x01010101u) & ~cy.w);
             bad |= (z & 0x80808080u) != 0;
         }
-        ov[i] = r;
+        if constexpr (NT_STORE) __builtin_nontemporal_store(r, ov + i);
+        else ov[i] = r;
     }
     // tail (< 16 elements)
     for (i64 j = (nvec << 4) + (i64)blockIdx.x * TAB8_THREADS + threadIdx.x; j < n; j += stride) {
@@ -985,43 +993,70 @@ int tab8_grid(i64 n)
     return (int)(blocks < cap ? blocks : cap);
 }
 
+// 2^k read once from an environment variable (a measurement / test knob in the style of GFA_RS_WPS); k = 62 means "never"
+static i64 tab8_env_pow2(const char *name, long dflt)
+{
+    const char *e = getenv(name);
+    const long k = e ? strtol(e, nullptr, 10) : dflt;
+    return (i64)1 << (k < 0 ? 0 : k > 62 ? 62 : k);
+}
+
+template <bool CHECK_ZERO_B, bool NT_STORE>
+static int launch_tab8_static(int grid, const uint8_t *table, const void *a, const void *b, void *out, i64 n, hipStream_t st,
+                              int32_t *err)
+{
+    static bool attr = false; // one flag per instantiation
+    auto k = tab8_binary_kernel<CHECK_ZERO_B, NT_STORE>;
+    if (!attr) { GFA_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, 65536)); attr = true; }
+    hipLaunchKernelGGL(k, dim3(grid), dim3(TAB8_THREADS), 65536, st, table, (const uint8_t *)a, (const uint8_t *)b, (uint8_t *)out,
+                       n, err);
+    GFA_HIP(hipGetLastError());
+    return GFA_OK;
+}
+
+template <bool CHECK_ZERO_B>
+static int launch_tab8_claim(int grid, const uint8_t *table, const void *a, const void *b, void *out, i64 n, hipStream_t st,
+                             int32_t *err)
+{
+    static bool attr = false;
+    auto k = tab8_binary_claim_kernel<CHECK_ZERO_B>;
+    if (!attr) { GFA_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, 65536)); attr = true; }
+    // The counter is this launch's own (stream-ordered allocation) and its reset is a node of the same stream, so concurrent
+    // streams share nothing and a captured graph resets it on every replay.
+    unsigned int *counter = nullptr;
+    GFA_HIP(gfa::scratch_alloc((void **)&counter, sizeof(unsigned int), st));
+    GFA_HIP(hipMemsetAsync(counter, 0, sizeof(unsigned int), st));
+    hipLaunchKernelGGL(k, dim3(grid), dim3(TAB8_THREADS), 65536, st, table, (const uint8_t *)a, (const uint8_t *)b, (uint8_t *)out,
+                       n, err, counter);
+    GFA_HIP(hipGetLastError());
+    GFA_HIP(gfa::scratch_free(counter, st));
+    return GFA_OK;
+}
+
+// Which kernel by array size (tools/ubench/stream4.hip, profiles/r07_stream_order_*.txt; us per launch, medians):
+//                                  1e8      2^28     1e9
+//   static, ordinary stores       46.6     150.7    587.4
+//   static, non-temporal stores   44.1     145.7    572.9
+//   claimed 32 KiB blocks         58.3     138.4    485.4
+// so the claim kernel keeps its 2^28 lower bound (it loses below and wins from there), and the static kernel stores
+// non-temporally in the range where that was measured to win.  Its lower end, 2^26 elements, is NOT a measured crossover: it is
+// the size from which operands and result (3 x 64 MiB) no longer leave room in the 256 MiB Infinity Cache for a consumer to find
+// the result there; smaller arrays keep ordinary stores.  GFA_TAB8_NT_MIN_LOG=<k> and GFA_TAB8_CLAIM_MIN_LOG=<k> move the two
+// bounds to 2^k (62: never) so that tests and measurements reach every kernel at small sizes.
 int launch_tab8_binary(const uint8_t *table, bool check_zero_b, const void *a, const void *b, void *out, i64 n,
                        hipStream_t st, int32_t *err)
 {
+    static const i64 claim_min = tab8_env_pow2("GFA_TAB8_CLAIM_MIN_LOG", 28);
+    static const i64 nt_min = tab8_env_pow2("GFA_TAB8_NT_MIN_LOG", 26);
     const int grid = tab8_grid(n);
-    static bool attr[4] = {false, false, false, false};
-    if (n >= ((i64)1 << 28)) { // operands beyond the Infinity Cache: claimed blocks (see tab8_binary_claim_kernel)
-        unsigned int *counter = nullptr;
-        GFA_HIP(gfa::scratch_alloc((void **)&counter, sizeof(unsigned int), st));
-        GFA_HIP(hipMemsetAsync(counter, 0, sizeof(unsigned int), st));
-        if (check_zero_b) {
-            auto k = tab8_binary_claim_kernel<true>;
-            if (!attr[3]) { GFA_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, 65536)); attr[3] = true; }
-            hipLaunchKernelGGL(k, dim3(grid), dim3(TAB8_THREADS), 65536, st, table, (const uint8_t *)a, (const uint8_t *)b,
-                               (uint8_t *)out, n, err, counter);
-        } else {
-            auto k = tab8_binary_claim_kernel<false>;
-            if (!attr[2]) { GFA_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, 65536)); attr[2] = true; }
-            hipLaunchKernelGGL(k, dim3(grid), dim3(TAB8_THREADS), 65536, st, table, (const uint8_t *)a, (const uint8_t *)b,
-                               (uint8_t *)out, n, err, counter);
-        }
-        GFA_HIP(hipGetLastError());
-        GFA_HIP(gfa::scratch_free(counter, st));
-        return GFA_OK;
-    }
-    if (check_zero_b) {
-        auto k = tab8_binary_kernel<true>;
-        if (!attr[1]) { GFA_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, 65536)); attr[1] = true; }
-        hipLaunchKernelGGL(k, dim3(grid), dim3(TAB8_THREADS), 65536, st, table, (const uint8_t *)a, (const uint8_t *)b,
-                           (uint8_t *)out, n, err);
-    } else {
-        auto k = tab8_binary_kernel<false>;
-        if (!attr[0]) { GFA_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, 65536)); attr[0] = true; }
-        hipLaunchKernelGGL(k, dim3(grid), dim3(TAB8_THREADS), 65536, st, table, (const uint8_t *)a, (const uint8_t *)b,
-                           (uint8_t *)out, n, err);
-    }
-    GFA_HIP(hipGetLastError());
-    return GFA_OK;
+    if (n >= claim_min)
+        return check_zero_b ? launch_tab8_claim<true>(grid, table, a, b, out, n, st, err)
+                            : launch_tab8_claim<false>(grid, table, a, b, out, n, st, err);
+    if (n >= nt_min)
+        return check_zero_b ? launch_tab8_static<true, true>(grid, table, a, b, out, n, st, err)
+                            : launch_tab8_static<false, true>(grid, table, a, b, out, n, st, err);
+    return check_zero_b ? launch_tab8_static<true, false>(grid, table, a, b, out, n, st, err)
+                        : launch_tab8_static<false, false>(grid, table, a, b, out, n, st, err);
 }
 
 int launch_tab8_unary(const uint8_t *table256, bool check_zero, const void *a, void *out, i64 n, hipStream_t st,
