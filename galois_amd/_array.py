@@ -1576,3 +1576,11 @@ class FieldArray(metaclass=FieldArrayMeta):
     def null_space(self):
         from . import _linalg
         return _linalg.null_space(self)
+
+    def characteristic_poly(self):
+        from . import _linalg
+        return _linalg.characteristic_poly(self)
+
+    def minimal_poly(self):
+        from . import _linalg
+        return _linalg.minimal_poly(self)

@@ -8,7 +8,8 @@ Field linear algebra on device arrays: the host-side mirror of the reference's l
   * row_reduce / lu / plu .............. _domains/_linalg.py:315-424, FieldArray methods _fields/_array.py:1412-1540
   * det / matrix_rank / inv / solve .... _domains/_linalg.py:427-548
   * row/column/left-null/null space .... _fields/_array.py:1541-1760
-The arithmetic is gfa_matmul / gfa_row_reduce / gfa_plu_decompose (include/galois_amd.h); this module only checks
+  * characteristic_poly / minimal_poly . _fields/_array.py:1845-2125, helpers :2385-2461
+The arithmetic is gfa_matmul / gfa_row_reduce / gfa_plu_decompose / gfa_charpoly (include/galois_amd.h); this module only checks
 arguments, lays operands out and reproduces the reference's exception types.
 """
 from __future__ import annotations
@@ -375,3 +376,113 @@ def null_space(A: FieldArray) -> FieldArray:
     if not A.ndim == 2:
         raise ValueError(f"Only 2-D matrices have a null space, not {A.ndim}-D.")
     return left_null_space(A.T)
+
+
+# ---- characteristic and minimal polynomials ------------------------------------------------------------------------------
+def _charpoly_t(A: FieldArray, t: torch.Tensor) -> torch.Tensor:
+    """Coefficients of det(xI - M), highest degree first, of every matrix of a contiguous (batch, n, n) tensor: one gfa_charpoly call."""
+    cls = type(A)
+    batch, n, _ = t.shape
+    out = torch.empty((batch, n + 1), dtype=t.dtype, device=t.device)
+    L.check(L.lib().gfa_charpoly(cls._handle, _ptr(t), _ptr(out), batch, n, A._gfa_dtype(), _stream()), "gfa_charpoly")
+    return out
+
+
+def _matrix_limit(A: FieldArray):
+    cls = type(A)
+    if cls._limbed:
+        raise NotImplementedError(
+            f"The characteristic polynomial of a matrix is not implemented for {cls.name}: gfa_charpoly serves fields of order below 2^64."
+        )
+
+
+def characteristic_poly_batched(A: FieldArray) -> FieldArray:
+    """Device extension: characteristic polynomials of a (batch, n, n) stack in one call, as a (batch, n + 1) array of
+    coefficients, highest degree first."""
+    if not (A.ndim == 3 and A.shape[1] == A.shape[2]):
+        raise ValueError(f"Argument 'A' must be a stack of square matrices, not have shape {tuple(A.shape)}.")
+    _matrix_limit(A)
+    return _rewrap(A, _charpoly_t(A, A._t.contiguous()))
+
+
+def _element_limit(a: FieldArray, what: str):
+    cls = type(a)
+    if cls._limbed and cls._NL > 2:
+        raise NotImplementedError(f"The {what} polynomial of an element is not implemented for {cls.name}: it serves fields of order up to 2^128.")
+
+
+def _minimal_poly_element(a: FieldArray):
+    """_minimal_poly_element (_fields/_array.py:2433-2461): the product of (x - c) over the Frobenius orbit of a, re-read over GF(p)."""
+    from ._poly import Poly
+
+    cls = type(a)
+    _element_limit(a, "minimal")
+    if cls.is_prime_field:
+        return Poly(np.concatenate([cls.Ones(1, dtype=a.dtype), (-a).reshape(1)]))
+    p, m = cls._characteristic, cls._degree
+    # the orbit a, a^p, a^(p^2), ...: at most m values, told apart on the host as integers (np.unique does not serve two-limb fields)
+    orbit, seen = [], set()
+    conj = a
+    for _ in range(m):
+        v = int(conj)
+        if v in seen:
+            break
+        seen.add(v)
+        orbit.append(conj)
+        conj = np.power(conj, p)
+    one = cls.Ones(1, dtype=a.dtype)
+    prod = np.concatenate([one, (-orbit[0]).reshape(1)])
+    for c in orbit[1:]:
+        prod = np.convolve(prod, np.concatenate([one, (-c).reshape(1)]))
+    return Poly(cls.prime_subfield([int(v) for v in prod.numpy()]))  # the coefficients lie in GF(p): re-read there
+
+
+def _characteristic_poly_element(a: FieldArray):
+    """_characteristic_poly_element (_fields/_array.py:2385-2406): m_a(x)^(m / deg m_a)."""
+    from ._poly import Poly
+
+    cls = type(a)
+    _element_limit(a, "characteristic")
+    m_a = _minimal_poly_element(a)
+    if cls.is_prime_field:
+        return m_a
+    out = m_a
+    for _ in range(cls._degree // m_a.degree - 1):
+        out = out * m_a
+    return out
+
+
+def characteristic_poly(A: FieldArray):
+    """FieldArray.characteristic_poly (_fields/_array.py:1845-1977)."""
+    from ._poly import Poly
+
+    if A.ndim == 0:
+        return _characteristic_poly_element(A)
+    if A.ndim != 2:
+        raise ValueError(
+            f"The array must be either 0-D to return the characteristic polynomial of a single element "
+            f"or 2-D to return the characteristic polynomial of a square matrix, not have shape {tuple(A.shape)}."
+        )
+    if A.shape[0] != A.shape[1]:
+        raise ValueError(f"The 2-D array must be square to compute its characteristic polynomial, not have shape {tuple(A.shape)}.")
+    _matrix_limit(A)
+    t = A._t.contiguous()
+    return Poly(_rewrap(A, _charpoly_t(A, t.reshape(1, *t.shape))[0]))
+
+
+def minimal_poly(A: FieldArray):
+    """FieldArray.minimal_poly (_fields/_array.py:1979-2125).  The matrix form factors the characteristic polynomial in the
+    reference; polynomial factoring is outside this engine."""
+    if A.ndim == 0:
+        return _minimal_poly_element(A)
+    if A.ndim != 2:
+        raise ValueError(
+            f"The array must be either 0-D to return the minimal polynomial of a single element "
+            f"or 2-D to return the minimal polynomial of a square matrix, not have shape {tuple(A.shape)}."
+        )
+    if A.shape[0] != A.shape[1]:
+        raise ValueError(f"The 2-D array must be square to compute its minimal polynomial, not have shape {tuple(A.shape)}.")
+    raise NotImplementedError(
+        "The minimal polynomial of a matrix needs the factorization of its characteristic polynomial, and polynomial factoring "
+        "is outside this engine. Use characteristic_poly(), which the minimal polynomial divides."
+    )

@@ -284,6 +284,12 @@ int gfa_row_reduce(gfa_field_t *f, void *a, int64_t batch, int64_t m, int64_t n,
  * zero pivot above a non-zero entry ORs GFA_DEVERR_NO_LU into *dev_err. */
 int gfa_plu_decompose(gfa_field_t *f, void *a, void *l_out, void *p_out, int64_t batch, int64_t m, int64_t n, int pivoting,
                       int64_t *n_permutations_out, void *det_out, int dtype, gfa_stream_t stream, int32_t *dev_err);
+/* _characteristic_poly_matrix (_fields/_array.py:2409-2430, the matrix form of FieldArray.characteristic_poly, :1845-1977):
+ * coeffs_out[b] = the n + 1 coefficients of det(x I - a[b]), highest degree first (leading coefficient 1), for `batch`
+ * contiguous row-major (n x n) matrices.  `a` is NOT modified (the library works on a scratch copy).  The reference expands
+ * the determinant of a matrix of Poly objects; here: similarity reduction to Hessenberg form, then the Hessenberg recurrence --
+ * O(n^3), only pivots are inverted, every characteristic.  n == 0 writes the single coefficient 1; at most 4096 rows. */
+int gfa_charpoly(gfa_field_t *f, const void *a, void *coeffs_out, int64_t batch, int64_t n, int dtype, gfa_stream_t stream);
 
 /* ---- Reed-Solomon -------------------------------------------------------------------------------- *
  * gfa_rs_create replaces the arithmetic part of ReedSolomon.__init__ (_codes/_reed_solomon.py:111-218) and
