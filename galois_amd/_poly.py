@@ -5,7 +5,9 @@ array-sized work.  Paths relative to /roo
   * Poly.__call__ (element-wise and square-matrix evaluation) ... _polys/_poly.py:862-950 over evaluate_elementwise_jit /
                                                                  evaluate_matrix_jit (_polys/_dense.py:404-470)
   * + - * (polynomial and scalar), negation ..................... _polys/_dense.py:54-123 (multiply = np.convolve)
-Everything symbolic (factoring, gcd, irreducibility tests, sparse/binary representations) stays out of scope.
+  * is_irreducible() / is_primitive(), Int / Degrees / int() .... _polys/_irreducible.py:27-124, _primitive.py:26-104,
+                                                                 _poly.py:372-530 (the tests run in galois_amd/_polysearch.py)
+Everything symbolic (factoring, gcd, sparse/binary representations) stays out of scope.
 """
 from __future__ import annotations
 
@@ -49,6 +51,58 @@ class Poly:
         if nz.numel() == 0:
             return c[-1:] if c.size else c
         return c[int(nz[0].item()):]
+
+    @classmethod
+    def Int(cls, integer: int, field=None) -> "Poly":
+        """Poly.Int (_polys/_poly.py:372-444): the polynomial whose coefficients are the radix-q digits of the integer."""
+        if not isinstance(integer, (int, np.integer)):
+            raise TypeError(f"Argument 'integer' must be an instance of {int}, not {type(integer)}.")
+        if not integer >= 0:
+            raise ValueError(f"Argument 'integer' must be non-negative, not {integer}.")
+        if field is None:
+            from ._factory import GF
+
+            field = GF(2)
+        return cls(field(np.array(nt.poly_from_int(int(integer), field.order), dtype=object)))
+
+    @classmethod
+    def Degrees(cls, degrees, coeffs=None, field=None) -> "Poly":
+        """Poly.Degrees (_polys/_poly.py:447-530): the polynomial with the given non-zero degrees (coefficients default to 1)."""
+        degrees = [int(d) for d in degrees]
+        if any(d < 0 for d in degrees):
+            raise ValueError(f"Argument 'degrees' must have non-negative values, not {degrees}.")
+        if isinstance(coeffs, FieldArray):
+            if field is not None and type(coeffs) is not field:
+                raise TypeError(f"Argument 'coeffs' is over {type(coeffs).name} but 'field' is {field.name}.")
+            field = type(coeffs)
+            coeffs = coeffs.numpy()
+        coeffs = [1] * len(degrees) if coeffs is None else [int(c) for c in coeffs]
+        if len(coeffs) != len(degrees):
+            raise ValueError(f"Arguments 'degrees' and 'coeffs' must have the same length, not {len(degrees)} and {len(coeffs)}.")
+        if field is None:
+            from ._factory import GF
+
+            field = GF(2)
+        dense = [0] * (max(degrees, default=0) + 1)
+        for d, c in zip(degrees, coeffs):
+            dense[len(dense) - 1 - d] = c
+        return cls(field(np.array(dense, dtype=object)))
+
+    def __int__(self) -> int:
+        """The integer whose radix-q digits are the coefficients (_polys/_poly.py:752-775)."""
+        return nt.poly_to_int([int(v) for v in self._coeffs.numpy()], self._field.order)
+
+    def is_irreducible(self) -> bool:
+        """Poly.is_irreducible (_polys/_irreducible.py:27-124): Rabin's test, on the device (gfa_poly_classify)."""
+        from ._polysearch import _poly_test
+
+        return _poly_test(self, False)
+
+    def is_primitive(self) -> bool:
+        """Poly.is_primitive (_polys/_primitive.py:26-104): irreducible, non-zero constant term, and x of full order."""
+        from ._polysearch import _poly_test
+
+        return _poly_test(self, True)
 
     field = property(lambda self: self._field)
     coeffs = property(lambda self: self._coeffs)

@@ -290,6 +290,17 @@ int gfa_plu_decompose(gfa_field_t *f, void *a, void *l_out, void *p_out, int64_t
  * the determinant of a matrix of Poly objects; here: similarity reduction to Hessenberg form, then the Hessenberg recurrence --
  * O(n^3), only pivots are inverted, every characteristic.  n == 0 writes the single coefficient 1; at most 4096 rows. */
 int gfa_charpoly(gfa_field_t *f, const void *a, void *coeffs_out, int64_t batch, int64_t n, int dtype, gfa_stream_t stream);
+/* Poly.is_irreducible / Poly.is_primitive (_polys/_irreducible.py:101-124, _primitive.py:70-104) of `batch` polynomials of the
+ * same `degree` >= 1: coeffs is batch x (degree + 1) device elements, highest degree first, and is NOT modified.
+ * flags_out[i] (device): bit 0 = irreducible (Rabin's test); bit 1 = primitive, computed only when primitivity is asked for,
+ * i.e. when n_exps > 0 or cofactor_exps != NULL (q^degree - 1 = 1 has no prime divisor: GF(2), degree 1; with n_exps == 0 nothing
+ * is read through the pointer and exp_limbs is ignored).  cofactor_exps is
+ * HOST memory: the n_exps values (q^degree - 1) / r for the prime divisors r of q^degree - 1, each as exp_limbs little-endian
+ * 64-bit words.  A row whose leading coefficient is zero is not of the stated degree and gets 0x80; a non-monic row is
+ * classified as its monic multiple.  Degrees up to 255 over GF(2) (bit-packed), up to 32 over every other field of order
+ * below 2^64; beyond that GFA_ERR_UNSUPPORTED.  The host reads nothing back: two launches, the second on the irreducible rows. */
+int gfa_poly_classify(gfa_field_t *f, const void *coeffs, int64_t batch, int64_t degree, int dtype, const uint64_t *cofactor_exps,
+                      int64_t n_exps, int64_t exp_limbs, uint8_t *flags_out, gfa_stream_t stream);
 
 /* ---- Reed-Solomon -------------------------------------------------------------------------------- *
  * gfa_rs_create replaces the arithmetic part of ReedSolomon.__init__ (_codes/_reed_solomon.py:111-218) and
