@@ -20,6 +20,7 @@ from ._numtheory import (  # noqa: E402
 from ._polysearch import (  # noqa: E402
     irreducible_poly, irreducible_polys, primitive_polys, is_irreducible_batched, is_primitive_batched,
 )
+from ._polydiv import poly_divmod_batched, poly_powmod_batched  # noqa: E402
 from . import _dist as dist  # noqa: E402
 from . import _linalg as linalg  # noqa: E402
 
@@ -28,6 +29,6 @@ GF2 = GF(2)
 __all__ = [
     "FieldArray", "GF", "GF2", "Field", "ntt", "intt", "ReedSolomon", "BCH", "Poly", "berlekamp_massey", "is_prime", "factors", "primitive_root",
     "is_primitive_root", "matlab_primitive_poly", "conway_poly", "primitive_poly", "irreducible_poly", "irreducible_polys", "primitive_polys",
-    "is_irreducible_batched", "is_primitive_batched", "dist", "linalg",
+    "is_irreducible_batched", "is_primitive_batched", "poly_divmod_batched", "poly_powmod_batched", "dist", "linalg",
 ]
 __version__ = "0.1.0"

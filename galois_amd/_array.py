@@ -46,6 +46,11 @@ def _to_storage(t: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
     return wide.to(dtype)
 
 
+def _reflects(o) -> bool:
+    """True for operands that implement the reflected division operators themselves (galois_amd.Poly)."""
+    return getattr(type(o), "_reflected_division", False)
+
+
 def _unsigned_less(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """a < b on unsigned bit patterns held in signed torch storage (uint8 storage compares natively)."""
     if a.dtype == torch.uint8:
@@ -1335,14 +1340,15 @@ class FieldArray(metaclass=FieldArrayMeta):
     def __rmul__(self, o): return np.multiply(o, self)
     def __imul__(self, o):
         r = np.multiply(self, o); self._t = r._t; return self
-    def __truediv__(self, o): return np.true_divide(self, o)
+    # (a galois_amd.Poly on the right divides through its own reflected operators: field scalar // poly, % poly, divmod)
+    def __truediv__(self, o): return NotImplemented if _reflects(o) else np.true_divide(self, o)
     def __rtruediv__(self, o): return np.true_divide(o, self)
     def __itruediv__(self, o):
         r = np.true_divide(self, o); self._t = r._t; return self
-    def __floordiv__(self, o): return np.floor_divide(self, o)
+    def __floordiv__(self, o): return NotImplemented if _reflects(o) else np.floor_divide(self, o)
     def __rfloordiv__(self, o): return np.floor_divide(o, self)
-    def __mod__(self, o): return np.remainder(self, o)
-    def __divmod__(self, o): return np.divmod(self, o)
+    def __mod__(self, o): return NotImplemented if _reflects(o) else np.remainder(self, o)
+    def __divmod__(self, o): return NotImplemented if _reflects(o) else np.divmod(self, o)
     def __neg__(self): return np.negative(self)
     def __pos__(self): return np.positive(self)
     def __pow__(self, o): return np.power(self, o)  # _ufunc.py:715-719

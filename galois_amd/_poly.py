@@ -7,7 +7,10 @@ array-sized work.  Paths relative to /roo
   * + - * (polynomial and scalar), negation ..................... _polys/_dense.py:54-123 (multiply = np.convolve)
   * is_irreducible() / is_primitive(), Int / Degrees / int() .... _polys/_irreducible.py:27-124, _primitive.py:26-104,
                                                                  _poly.py:372-530 (the tests run in galois_amd/_polysearch.py)
-Everything symbolic (factoring, gcd, sparse/binary representations) stays out of scope.
+  * divmod, //, %, ** and three-argument pow() .................. _polys/_poly.py:1327-1460 over divmod_jit / floordiv_jit /
+                                                                 mod_jit / pow_jit (_polys/_dense.py:126-401; galois_amd/_polydiv.py)
+Everything built on the remainder (gcd, factoring, roots, interpolation, LFSRs) and the sparse/binary representations stay out of
+scope.
 """
 from __future__ import annotations
 
@@ -21,6 +24,8 @@ from ._array import FieldArray, _ptr, _stream
 
 class Poly:
     """Dense polynomial with coefficients in degree-descending order, held as a 1-D device field array."""
+
+    _reflected_division = True  # FieldArray's / // % divmod hand a Poly on the right to the reflected operators below
 
     def __init__(self, coeffs, field=None, order: str = "desc"):
         if order not in ["desc", "asc"]:
@@ -196,6 +201,44 @@ class Poly:
         return Poly(np.convolve(self._coeffs, o._coeffs))
 
     __rmul__ = __mul__
+
+    # division with remainder and powers (galois_amd/_polydiv.py): gfa_poly_divmod / gfa_poly_powmod
+    def __divmod__(self, other):
+        from ._polydiv import poly_divmod
+
+        return poly_divmod(self, self._coerce(other))
+
+    def __rdivmod__(self, other):
+        return divmod(self._coerce(other), self)
+
+    def __floordiv__(self, other):
+        from ._polydiv import poly_divmod
+
+        return poly_divmod(self, self._coerce(other), want_r=False)[0]
+
+    def __rfloordiv__(self, other):
+        return self._coerce(other) // self
+
+    def __mod__(self, other):
+        from ._polydiv import poly_divmod
+
+        return poly_divmod(self, self._coerce(other), want_q=False)[1]  # the kernel writes no quotients
+
+    def __rmod__(self, other):
+        return self._coerce(other) % self
+
+    def __truediv__(self, other):
+        raise NotImplementedError(
+            "Polynomial true division is not supported because fractional polynomials are not yet supported. "
+            "Use floor division //, modulo %, and/or divmod() instead."
+        )
+
+    __rtruediv__ = __truediv__
+
+    def __pow__(self, exponent, modulus=None):
+        from ._polydiv import poly_pow
+
+        return poly_pow(self, exponent, None if modulus is None else self._coerce(modulus))
 
     def derivative(self, k: int = 1) -> "Poly":
         """Formal derivative (_polys/_poly.py:1098-1160): coefficient of x^(j-1) is (j mod p) * a_j."""

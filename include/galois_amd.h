@@ -301,6 +301,25 @@ int gfa_charpoly(gfa_field_t *f, const void *a, void *coeffs_out, int64_t batch,
  * below 2^64; beyond that GFA_ERR_UNSUPPORTED.  The host reads nothing back: two launches, the second on the irreducible rows. */
 int gfa_poly_classify(gfa_field_t *f, const void *coeffs, int64_t batch, int64_t degree, int dtype, const uint64_t *cofactor_exps,
                       int64_t n_exps, int64_t exp_limbs, uint8_t *flags_out, gfa_stream_t stream);
+/* divmod_jit / floordiv_jit / mod_jit (_polys/_dense.py:126-320) for `batch` dividends and ONE divisor: a is batch x na device
+ * coefficients, row-major, highest degree first (leading zeros allowed and kept); b is nb coefficients with b[0] != 0 and
+ * 1 <= nb <= na.  q_out receives batch x (na - nb + 1) quotient and r_out batch x (nb - 1) remainder coefficients, neither
+ * trimmed; either may be NULL and is then not computed for (Poly.__mod__ and the power below write no quotients).  With nb == 1
+ * r_out is not touched.  The outputs do not alias the inputs.  The values are divmod_jit.implementation's.  b[0] == 0 is a caller
+ * error the entry point cannot see (device memory): the call still terminates inside its buffers, with unspecified values.
+ * One workgroup per row, blocked synthetic division (gfa_polydiv.h); no degree cap -- a single long division is quadratic work
+ * on one compute unit.  At most 2^31 - 1 rows of at most 2^31 - 1 coefficients (GFA_ERR_UNSUPPORTED beyond). */
+int gfa_poly_divmod(gfa_field_t *f, const void *a, int64_t batch, int64_t na, const void *b, int64_t nb, void *q_out, void *r_out, int dtype,
+                    gfa_stream_t stream);
+/* pow_jit with a modulus (_polys/_dense.py:323-401) for `batch` bases, ONE exponent and ONE modulus: out is batch x (nc - 1)
+ * untrimmed coefficients of a_k(x)^e mod c(x).  a is batch x na (any na >= 1; a row is reduced modulo c first), c is nc >= 2
+ * coefficients with c[0] != 0, e >= 0 is n_limbs >= 1 little-endian 64-bit words in HOST memory (as the exponents of
+ * gfa_poly_classify).  e == 0 gives 1, also for a zero row.  The whole square-and-multiply chain is one launch with the
+ * operands in LDS, which caps the degree nc - 1 at 7654 for fields with 32-bit elements in the kernels (prime fields below
+ * 2^32 and table fields) and at 3814 for the others; above the cap GFA_ERR_UNSUPPORTED with a message that names it (loop over
+ * gfa_convolve and gfa_poly_divmod instead, as galois_amd/_polydiv.py does). */
+int gfa_poly_powmod(gfa_field_t *f, const void *a, int64_t batch, int64_t na, const uint64_t *exp_limbs, int64_t n_limbs, const void *c,
+                    int64_t nc, void *out, int dtype, gfa_stream_t stream);
 
 /* ---- Reed-Solomon -------------------------------------------------------------------------------- *
  * gfa_rs_create replaces the arithmetic part of ReedSolomon.__init__ (_codes/_reed_solomon.py:111-218) and
