@@ -117,3 +117,38 @@ def load_sage_polys(tag):
     d = np.load(os.path.join(GOLDEN, f"sage_polys_{tag}.npz"))
     props = json.loads(str(d["properties"]))
     return props, d
+
+
+def projection_width(q):
+    """Number of random vectors with which a wrong product passes the projection check with probability at most 2^-32:
+    the smallest nvec with q^nvec >= 2^32, i.e. ceil(32 / log2 q)."""
+    nvec = 1
+    while q**nvec < 2**32:
+        nvec += 1
+    return nvec
+
+
+def python_int_matmul(p):
+    """Matrix product over GF(p) in Python integers (the 64-bit primes): exact whatever the size of p."""
+    return lambda X, Y: (np.asarray(X).astype(object) @ np.asarray(Y).astype(object)) % p
+
+
+def assert_product_by_projection(mul_mat, A, B, C, q, rng, label=""):
+    """Freivalds' check of C == A B over GF(q) on EVERY entry of C: with V uniform in GF(q)^(N x nvec), C V == A (B V).
+    If C != A B, some row of D = C - A B is non-zero and D V = 0 holds with probability q^-nvec <= 2^-32 over V.  mul_mat is
+    the checker's matrix product (the oracle's, or python_int_matmul): three thin products instead of the M x K x N one."""
+    A, B, C = np.asarray(A), np.asarray(B), np.asarray(C)
+    assert A.ndim == B.ndim == 2 and C.shape == (A.shape[0], B.shape[1]), f"{label}: shape {C.shape}"
+    assert all(0 <= int(v) < q for v in (C.min(), C.max())), f"{label}: entry outside the field"
+    V = rng.integers(0, q, (B.shape[1], projection_width(q)), dtype=np.uint64)
+    assert_equal_ints(mul_mat(C, V), mul_mat(A, mul_mat(B, V)), f"{label}: C V != A (B V)")
+
+
+def exact_prime_matmul(A, B, p):
+    """(A B) mod p for a prime p <= 251 in float64: every partial sum is an integer below K (p - 1)^2 < 2^53, so the BLAS
+    product is exact whatever its summation order.  Independent of the oracle and of the device code."""
+    A, B = np.asarray(A), np.asarray(B)
+    assert 2 <= p <= 251 and all(p % d for d in range(2, p) if d * d <= p), f"{p} is not a prime up to 251"
+    assert A.shape[-1] * (p - 1) ** 2 < 2**53
+    assert 0 <= A.min() and A.max() < p and 0 <= B.min() and B.max() < p
+    return ((A.astype(np.float64) @ B.astype(np.float64)) % p).astype(np.uint64)

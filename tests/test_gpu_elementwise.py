@@ -1576,8 +1576,8 @@ def test_folds_and_scans_of_long_rows_on_two_streams_at_once():
 @pytest.mark.parametrize("order", [2**8, 2**4, 2**16, 2**20, 2**32, 3**5, 7**3, 3**2, 5**4, 3**10, 31**2])
 def test_long_polynomial_products_over_extension_fields(order):
     """r06: np.convolve over GF(2^m) / GF(p^m) from 2^20 coefficient products: Karatsuba over the bit / digit positions, every leaf an exact
-    integer convolution modulo one transform prime (gfa_conv_crt.hip::run_planes) -- against the direct kernel's values through the oracle
-    on short operands, and for long ones through evaluation: c(x0) == a(x0) b(x0) at random points (Horner with the oracle), plus the full
+    integer convolution modulo one transform prime (gfa_conv_crt.hip::run_planes) -- every coefficient of every shape against the oracle's
+    product, and through evaluation: c(x0) == a(x0) b(x0) at random points (Horner with the oracle), plus the full
     comparison with the direct kernel of a child process (GFA_CONV_PLANES_MIN_LOG=62)."""
     GF = ga.GF(order)
     p, m = GF.characteristic, GF.degree
@@ -1598,11 +1598,12 @@ def test_long_polynomial_products_over_extension_fields(order):
         assert len(c) == na + nb - 1
         x0 = rng.integers(0, order, 6, dtype=np.uint64)
         H.assert_equal_ints(horner(c, x0), F.mul(horner(a, x0), horner(b, x0)), f"GF({order}) {na} x {nb}: c(x) == a(x) b(x)")
-        if na * nb <= 1100 * 1100:  # every coefficient against the oracle's schoolbook product
-            want = np.zeros(na + nb - 1, dtype=np.uint64)
-            for i in range(nb):
-                want[i:i + na] = F.add(want[i:i + na], F.mul(a, np.full(na, b[i], dtype=np.uint64)))
-            H.assert_equal_ints(c, want, f"GF({order}) {na} x {nb}")
+        # every coefficient, at every shape, against the oracle's schoolbook product (row by row) and its convolution
+        want = np.zeros(na + nb - 1, dtype=np.uint64)
+        for i in range(nb):
+            want[i:i + na] = F.add(want[i:i + na], F.mul(a, np.full(na, b[i], dtype=np.uint64)))
+        H.assert_equal_ints(c, want, f"GF({order}) {na} x {nb}")
+        H.assert_equal_ints(c, F.convolve(a, b), f"GF({order}) {na} x {nb} against the oracle's convolution")
 
 
 def test_long_polynomial_products_agree_with_the_direct_kernel():
@@ -1630,3 +1631,56 @@ def test_long_polynomial_products_agree_with_the_direct_kernel():
             res[tag] = dict(np.load(path))
         for q in res["planes"]:
             assert np.array_equal(res["planes"][q], res["direct"][q]), q
+
+
+@pytest.mark.parametrize("order", [2**8, 2**16, 3**5, 7**3, 3**10, 2**32])
+def test_long_polynomial_products_against_the_oracle(order):
+    """The 3000 x 2500 product that the child-process test compares between the project's two kernels only: every coefficient against the
+    oracle's convolution."""
+    GF = ga.GF(order)
+    F = O.OracleField(GF.characteristic, GF.degree, int(GF.irreducible_poly), int(GF.primitive_element), lookup=order <= 2**16)
+    rng = np.random.default_rng(order % 997 + 11)
+    a, b = rng.integers(0, order, 3000, dtype=np.uint64), rng.integers(0, order, 2500, dtype=np.uint64)
+    a[0] = b[-1] = order - 1
+    dt = GF.dtypes[0]
+    c = np.convolve(GF(a.astype(dt), dtype=dt), GF(b.astype(dt), dtype=dt)).numpy().astype(np.uint64)
+    H.assert_equal_ints(c, F.convolve(a, b), f"GF({order}) 3000 x 2500")
+
+
+def _plane_route_longest(p):
+    """The plane route's exactness rule (gfa_conv_crt.hip::planes_eligible): min(na, nb) (p - 1)^2 < 0.99 * 469762049, every integer
+    coefficient of a plane product below the transform prime.  Returns the longest shorter operand it admits (integer arithmetic)."""
+    lo = (99 * 469762049 - 1) // (100 * (p - 1) ** 2)
+    assert 100 * lo * (p - 1) ** 2 < 99 * 469762049 <= 100 * (lo + 1) * (p - 1) ** 2
+    return lo
+
+
+@pytest.mark.parametrize("order,na,nbs", [(251**2, 9000, (0, 1)), (251**3, None, (0,)), (127**2, 9000, (9000,))],
+                         ids=["gf251e2", "gf251e3", "gf127e2"])
+def test_polynomial_products_at_the_plane_routes_exactness_bound(order, na, nbs):
+    """Characteristic 251 at the longest shorter operand the plane route admits (7441 for p = 251, derived from the rule) and one past
+    it, where the direct kernel takes over; a and b hold q - 1 (every digit p - 1: the largest plane values) in their first three
+    quarters and random elements after.  Over GF(251^2) also operands of q - 1 throughout, whose middle coefficients are sums of
+    7441 * 250^2 = 465062500 of the prime's 469762049.  GF(251^3) has no oracle tables (9000 x 7441 explicit products take 12.5 s on the
+    host): 7441 x 7441, the fewest products with the shorter operand at the bound.  GF(127^2) at 9000 x 9000 as a second characteristic.
+    Every coefficient against the oracle's convolution."""
+    GF = ga.GF(order)
+    p = GF.characteristic
+    F = O.OracleField(p, GF.degree, int(GF.irreducible_poly), int(GF.primitive_element), lookup=order <= 2**16)
+    rng = np.random.default_rng(order % 997 + 13)
+    dt = GF.dtypes[0]
+    longest = _plane_route_longest(p)
+    assert p != 251 or longest == 7441
+    na = longest if na is None else na
+    def fill(n):
+        v = rng.integers(0, order, n, dtype=np.uint64)
+        v[: 3 * n // 4] = order - 1
+        return v
+    conv = lambda a, b: np.convolve(GF(a.astype(dt), dtype=dt), GF(b.astype(dt), dtype=dt)).numpy().astype(np.uint64)
+    for nb in nbs:
+        nb = nb if nb > 1 else longest + nb
+        a, b = fill(na), fill(nb)
+        H.assert_equal_ints(conv(a, b), F.convolve(a, b), f"GF({order}) {na} x {nb}")
+    if order == 251**2:
+        a, b = np.full(na, order - 1, dtype=np.uint64), np.full(longest, order - 1, dtype=np.uint64)
+        H.assert_equal_ints(conv(a, b), F.convolve(a, b), f"GF({order}) {na} x {longest}, q - 1 throughout")

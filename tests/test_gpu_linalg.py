@@ -288,6 +288,7 @@ def test_odd_characteristic_extension_field_matmul_on_matrix_cores(order):
     GF = ga.GF(order)
     F = O.OracleField(GF.characteristic, GF.degree, int(GF.irreducible_poly), int(GF.primitive_element), lookup=order <= 2**16)
     rng = np.random.default_rng(order % 9973)
+    prng = np.random.default_rng(order % 9973 + 1)  # the projection vectors: a stream of their own, the operands stay what they were
     small = order > 2**16  # (no oracle tables there: its explicit arithmetic sets the pace, so a sample of rows x columns is compared)
     shapes = ([(256, 256, 256), (130, 1100, 129)] if small else [(256, 64, 256), (300, 500, 257), (128, 1100, 129)]) + ([(512, 512, 512)] if order in (3**5, 251**2) else [])
     for M, K, N in shapes:
@@ -298,6 +299,8 @@ def test_odd_characteristic_extension_field_matmul_on_matrix_cores(order):
         for dt in GF.dtypes[:1] + GF.dtypes[-1:]:
             got = (GF(A.astype(dt), dtype=dt) @ GF(B.astype(dt), dtype=dt)).numpy()
             H.assert_equal_ints(got[np.ix_(rows, cols)], want, f"GF({order}) {M}x{K}x{N} {np.dtype(dt).name}")
+            if small:  # every entry of C: C V == A (B V) for random V (wrong with probability <= 2^-32)
+                H.assert_product_by_projection(F.matmul, A, B, got, order, prng, f"GF({order}) {M}x{K}x{N} {np.dtype(dt).name}")
     K = 2001 if small else 20001
     A, B = np.full((128, K), order - 1), np.full((K, 130), order - 1)
     sq = int(F.mul(np.array([order - 1], dtype=np.uint64), np.array([order - 1], dtype=np.uint64))[0])
@@ -307,6 +310,10 @@ def test_odd_characteristic_extension_field_matmul_on_matrix_cores(order):
     C = (GF(A3) @ GF(B1)).numpy()
     for i in range(2):
         H.assert_equal_ints(C[i][:3], F.matmul(A3[i][:3], B1), f"stack {i}")
+        if small:
+            H.assert_product_by_projection(F.matmul, A3[i], B1, C[i], order, prng, f"GF({order}) stack {i}")
+        else:
+            H.assert_equal_ints(C[i], F.matmul(A3[i], B1), f"GF({order}) stack {i}, every row")
 
 
 def test_binary_extension_field_matmul_agrees_with_the_table_kernels():
@@ -352,6 +359,7 @@ def test_64_bit_prime_matmul_on_matrix_cores(p):
     for i in (0, 2047):
         want = (a[i].astype(object) @ Bo) % p
         assert [int(v) for v in C[i]] == [int(v) for v in want], (p, i)
+    H.assert_product_by_projection(H.python_int_matmul(p), a, b, C, p, np.random.default_rng(61), f"GF({p}) {M}x{K}x{N}")  # every entry
     ones_a, ones_b = np.full((256, 9000), p - 1, dtype=np.uint64), np.full((9000, 4096), p - 1, dtype=np.uint64)
     got = (wrap(ones_a) @ wrap(ones_b)).numpy()
     assert all(int(v) == (9000 * pow(p - 1, 2, p)) % p for v in got[::37, ::41].ravel())
@@ -381,3 +389,168 @@ def test_exceptions():
     H2 = ga.GF(2)([[1, 0, 1, 0, 1, 0, 1, 0], [0, 1, 1, 0, 0, 1, 1, 0], [0, 0, 0, 1, 1, 1, 1, 0], [1, 1, 1, 1, 1, 1, 1, 1]])
     assert np.array_equal(H2.row_reduce(eye="right").numpy(), [[0, 1, 1, 1, 1, 0, 0, 0], [1, 0, 1, 1, 0, 1, 0, 0],
                                                               [1, 1, 0, 1, 0, 0, 1, 0], [1, 1, 1, 0, 0, 0, 0, 1]])
+
+
+# ---- every entry of the plane and limb products, and the edges of their exactness rules ---------------------------------------------
+# References cheap enough for every output: the float64 product for p <= 251, the oracle's table loop up to 2^16 elements, the projection
+# check (tests/helpers.py, host-tested in test_product_references_host.py) above that.  The shapes follow from the eligibility rules of
+# gfa_matmul_mfma.hip (restated below where a test derives a size from them); no test looks at which kernel ran -- the values must be
+# right whichever does.
+
+def _oracle(GF):
+    if GF.degree == 1:
+        return O.OracleField(GF.characteristic, 1, None, int(GF.primitive_element))
+    return O.OracleField(GF.characteristic, GF.degree, int(GF.irreducible_poly), int(GF.primitive_element), lookup=GF.order <= 2**16)
+
+
+def _upload(GF, v, dt=None):
+    """Host integers -> field array: the 64-bit primes are stored as uint64 words (dtype=object in the reference)."""
+    if GF.order > 2**32:
+        import torch
+
+        return GF._wrap(torch.from_numpy(np.ascontiguousarray(v, dtype=np.uint64).view(np.int64)).cuda(), np.object_)
+    dt = GF.dtypes[0] if dt is None else dt
+    return GF(v.astype(dt), dtype=dt)
+
+
+def _limb_rule(p):
+    """The limb path's rule (matmul_mfma_eligible): nl = ceil(bits(p) / 7) limbs, the longest K with nl K 127^2 < 2^31, and the smallest
+    M = N >= 64 that reaches the path's multiply-add threshold (2^27 up to five limbs, 2^33 above) at that K."""
+    nl = -(-p.bit_length() // 7)
+    kmax = (2**31 - 1) // (nl * 127 * 127)
+    assert nl * kmax * 127 * 127 < 2**31 <= nl * (kmax + 1) * 127 * 127
+    n = 64
+    while n * n * kmax < 2 ** (27 if nl <= 5 else 33):
+        n += 1
+    return nl, kmax, n
+
+
+@pytest.mark.parametrize("p", [2**64 - 2**32 + 1, 2**61 - 1])
+def test_64_bit_prime_ragged_matmul_every_entry(p):
+    """2050 x 2100 x 2049: still 2^33 multiply-adds with M N <= 2^26, on the 256 x 256 tiles with neither dimension a multiple of 256 (so the
+    100 limb products are launched one by one, not merged over the rows) -- every entry through the projection check in Python integers."""
+    GF = ga.GF(p)
+    rng = np.random.default_rng(p % 1009)
+    M, K, N = 2050, 2100, 2049
+    assert M * N * K >= 2**33 and M * N <= 2**26
+    a, b = _rand(rng, p, (M, K)), _rand(rng, p, (K, N))
+    a[-1, -1], a[-2, 0], b[-1, -1] = p - 1, 0, p - 1
+    C = (_upload(GF, a) @ _upload(GF, b)).numpy()
+    H.assert_product_by_projection(H.python_int_matmul(p), a, b, C, p, rng, f"GF({p}) {M}x{K}x{N}")
+
+
+@pytest.mark.parametrize("order", [2, 3, 251, 3**5, 251**2, 2**8, 13**5])
+def test_256_tile_matmul_every_entry(order):
+    """M, N >= 1024 selects the 256 x 256 block tile (16 waves): one shape with M and N just past a multiple of 256 -- the last tile row
+    and column hold 6 and 1 live rows / columns -- and one of whole tiles with N != M, on the prime path, the digit planes and the bit
+    planes, first and last storage dtype, every output compared."""
+    GF = ga.GF(order)
+    F = _oracle(GF)
+    rng = np.random.default_rng(order % 9973 + 256)
+    for M, K, N in [(1030, 100, 1025), (1024, 128, 1280)]:
+        A, B = rng.integers(0, order, (M, K)), rng.integers(0, order, (K, N))
+        A[-1], B[:, -1] = order - 1, order - 1
+        if GF.degree == 1:
+            want = H.exact_prime_matmul(A, B, order)
+        elif order <= 2**16:
+            want = F.matmul(A, B)
+        for dt in GF.dtypes[:1] + GF.dtypes[-1:]:
+            got = (GF(A.astype(dt), dtype=dt) @ GF(B.astype(dt), dtype=dt)).numpy()
+            label = f"GF({order}) {M}x{K}x{N} {np.dtype(dt).name}"
+            if order <= 2**16:
+                H.assert_equal_ints(got, want, label)
+            else:
+                H.assert_product_by_projection(F.matmul, A, B, got, order, rng, label)
+
+
+@pytest.mark.parametrize("p", [65537, 2147483647])
+def test_256_tile_limb_matmul_every_entry(p):
+    """The limb products (int32 sums ADDED to the diagonal buffers) on the 256 x 256 tiles: 1030 x 130 x 1025 takes the nl^2 launches with
+    ragged last tiles, 1024 x 128 x 1024 the launch merged over the nl M rows -- both at the path's 2^27 multiply-adds, against the oracle."""
+    GF = ga.GF(p)
+    F = _oracle(GF)
+    rng = np.random.default_rng(p % 1000 + 256)
+    for M, K, N in [(1030, 130, 1025), (1024, 128, 1024)]:
+        assert M * N * K >= 2**27
+        A, B = rng.integers(0, p, (M, K)), rng.integers(0, p, (K, N))
+        A[-1], B[:, -1] = p - 1, p - 1
+        want = F.matmul(A, B)
+        for dt in (GF.dtypes[0], np.int64):
+            got = (GF(A.astype(dt), dtype=dt) @ GF(B.astype(dt), dtype=dt)).numpy()
+            H.assert_equal_ints(got, want, f"GF({p}) {M}x{K}x{N} {np.dtype(dt).name}")
+
+
+@pytest.mark.parametrize("order,big", [(31, None), (65537, (560, 500, 520)), (2**8, (200, 600, 150)), (3**5, (200, 600, 150))])
+def test_matmul_with_the_first_operand_broadcast(order, big):
+    """One 2-D A against a stack of B (every other stack test broadcasts B): A is staged once and its batch stride is zero.  200 x 300 x 150
+    reaches the matrix cores over GF(31) only -- the planes start at 2^24 multiply-adds and the limbs at 2^27 -- so the other fields also
+    run the smallest convenient shape past their path's threshold.  Every member against the oracle; the large GF(65537) product against
+    the exact int64 product (K (p - 1)^2 < 2^63), which costs a twentieth of the oracle's loop."""
+    GF = ga.GF(order)
+    F = _oracle(GF)
+    rng = np.random.default_rng(order % 9973 + 3)
+    assert big is None or big[0] * big[1] * big[2] >= 2 ** (27 if order == 65537 else 24)
+    for M, K, N in [(200, 300, 150)] + ([big] if big else []):
+        A1, B3 = rng.integers(0, order, (M, K)), rng.integers(0, order, (3, K, N))
+        C = (GF(A1) @ GF(B3)).numpy()
+        assert C.shape == (3, M, N)
+        for i in range(3):
+            if order == 65537 and M * K * N >= 2**27:
+                assert K * (order - 1) ** 2 < 2**63
+                want = (A1.astype(np.int64) @ B3[i].astype(np.int64)) % order
+            else:
+                want = F.matmul(A1, B3[i])
+            H.assert_equal_ints(C[i], want, f"GF({order}) {M}x{K}x{N} member {i}")
+
+
+@pytest.mark.parametrize("order", [251, 3, 251**2])
+def test_centred_accumulators_filled_to_the_cap(order):
+    """K = 131072, the cap of the centred paths, with operands that centre to +-(p - 1)/2 instead of -1: A holds (p - 1)/2 (all digits, for
+    the extension field), B holds (p + 1)/2 -- which centres to -(p - 1)/2 -- in its even columns and (p - 1)/2 in its odd ones, so the int32
+    accumulators reach -K ((p - 1)/2)^2 and +K ((p - 1)/2)^2 (2.048e9 of 2^31 for p = 251).  Expected values from the oracle's 1 x K by K x 2
+    product, cross-checked against K times the scalar product; every output compared.  K = 131073 is past the cap (another kernel): same
+    rule, same values."""
+    GF = ga.GF(order)
+    F = _oracle(GF)
+    p, m = GF.characteristic, GF.degree
+    rep = (order - 1) // (p - 1)  # 1 + p + ... + p^(m-1): every digit one
+    lo, hi = (p - 1) // 2 * rep, (p + 1) // 2 * rep
+    dt = GF.dtypes[0]
+    n = 128
+    for K in (131072, 131073):
+        A = np.full((n, K), lo, dtype=dt)
+        B = np.full((K, n), lo, dtype=dt)
+        B[:, 0::2] = hi
+        want = F.matmul(A[:1], B[:, :2])[0]
+        for e, b in zip(want, (hi, lo)):  # K copies of one product: (K mod p) times it, digit by digit
+            sq = int(F.mul(np.array([lo], dtype=np.uint64), np.array([b], dtype=np.uint64))[0])
+            assert int(e) == sum((K * (sq // p**i % p)) % p * p**i for i in range(m))
+        C = (GF(A, dtype=dt) @ GF(B, dtype=dt)).numpy().astype(np.uint64)
+        assert C.shape == (n, n)
+        assert np.all(C[:, 0::2] == want[0]) and np.all(C[:, 1::2] == want[1]), (order, K)
+
+
+@pytest.mark.parametrize("p", [65537, 7340033, 2147483647, 2**61 - 1, 2**64 - 2**32 + 1])
+def test_limb_accumulators_filled_to_the_rule(p):
+    """Operands filled with v = 2^(bits(p) - 1) - 1, whose limbs below the top one are all 127, at the longest K the rule
+    nl K 127^2 < 2^31 admits (the middle diagonal then holds K (nl - 1) 127^2 or more) and at K + 1, where the rule hands over to another
+    kernel: K v^2 mod p everywhere.  Then random rows and columns among the all-v ones at the longest K, against the oracle up to five
+    limbs and through the projection check above.  M = N is the smallest size that reaches the path's multiply-add threshold."""
+    GF = ga.GF(p)
+    nl, kmax, n = _limb_rule(p)
+    v = 2 ** (p.bit_length() - 1) - 1
+    assert v < p and all((v >> (7 * l)) & 127 == 127 for l in range((p.bit_length() - 1) // 7))
+    for K in (kmax, kmax + 1):
+        A, B = np.full((n, K), v, dtype=np.uint64), np.full((K, n), v, dtype=np.uint64)
+        C = (_upload(GF, A) @ _upload(GF, B)).numpy()
+        assert C.shape == (n, n)
+        assert np.all(C == (K * v * v) % p), (p, K)
+    rng = np.random.default_rng(p % 1000 + 7)
+    A, B = np.full((n, kmax), v, dtype=np.uint64), np.full((kmax, n), v, dtype=np.uint64)
+    rows, cols = rng.choice(n, n // 4, replace=False), rng.choice(n, n // 4, replace=False)
+    A[rows], B[:, cols] = _rand(rng, p, (len(rows), kmax)), _rand(rng, p, (kmax, len(cols)))
+    C = (_upload(GF, A) @ _upload(GF, B)).numpy()
+    if nl <= 5:
+        H.assert_equal_ints(C, _oracle(GF).matmul(A, B), f"GF({p}) mixed rows at K = {kmax}")
+    else:
+        H.assert_product_by_projection(H.python_int_matmul(p), A, B, C, p, rng, f"GF({p}) mixed rows at K = {kmax}")
