@@ -319,11 +319,12 @@ int launch_charpoly_ft(const FieldDev &fd, const void *a, void *out, i64 batch, 
     T *H = nullptr, *P = nullptr;
     u64 *Tb = nullptr, *factor = nullptr;
     int *has = nullptr;
-    GFA_HIP(gfa::scratch_alloc((void **)&H, sizeof(T) * (size_t)(slice * n * n), st));
-    GFA_HIP(gfa::scratch_alloc((void **)&P, sizeof(T) * (size_t)(slice * tri(n + 1)), st));
-    GFA_HIP(gfa::scratch_alloc((void **)&Tb, sizeof(u64) * (size_t)(2 * slice * (n + 1)), st));
-    GFA_HIP(gfa::scratch_alloc((void **)&factor, sizeof(u64) * (size_t)(slice * n), st));
-    GFA_HIP(gfa::scratch_alloc((void **)&has, sizeof(int) * (size_t)slice, st));
+    Scratch ws(st);
+    GFA_HIP(ws.get(&H, (size_t)(slice * n * n)));
+    GFA_HIP(ws.get(&P, (size_t)(slice * tri(n + 1))));
+    GFA_HIP(ws.get(&Tb, (size_t)(2 * slice * (n + 1))));
+    GFA_HIP(ws.get(&factor, (size_t)(slice * n)));
+    GFA_HIP(ws.get(&has, (size_t)slice));
     u64 *Tbuf[2] = {Tb, Tb + slice * (n + 1)};
     for (i64 b0 = 0; b0 < batch; b0 += slice) {
         const i64 nb = batch - b0 < slice ? batch - b0 : slice;
@@ -348,11 +349,6 @@ int launch_charpoly_ft(const FieldDev &fd, const void *a, void *out, i64 batch, 
         hipLaunchKernelGGL((cp_write_kernel<T>), dim3((unsigned)((n + 1 + 255) / 256), (unsigned)nb), dim3(256), 0, st, P, o, (int)n);
         GFA_HIP(hipGetLastError());
     }
-    GFA_HIP(gfa::scratch_free(H, st));
-    GFA_HIP(gfa::scratch_free(P, st));
-    GFA_HIP(gfa::scratch_free(Tb, st));
-    GFA_HIP(gfa::scratch_free(factor, st));
-    GFA_HIP(gfa::scratch_free(has, st));
     return GFA_OK;
 }
 

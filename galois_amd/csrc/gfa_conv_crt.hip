@@ -136,7 +136,8 @@ int run_crt_set(gfa_field *f, const void *a, i64 na, const void *b, i64 nb, void
     int rc = aux_fields(SET, aux);
     if (rc) return rc;
     u32 *buf = nullptr;
-    GFA_HIP(gfa::scratch_alloc((void **)&buf, sizeof(u32) * 6 * (size_t)n_fft, st));
+    Scratch ws(st);
+    GFA_HIP(ws.get(&buf, 6 * (size_t)n_fft));
     const int grid = (int)std::min<i64>((n_fft + 255) / 256, 256 * 16);
     hipLaunchKernelGGL((crt_spread_kernel<T, SET>), dim3(grid), dim3(256), 0, st, (const T *)a, na, (const T *)b, nb, buf, n_fft);
     rc = GFA_OK;
@@ -162,7 +163,6 @@ int run_crt_set(gfa_field *f, const void *a, i64 na, const void *b, i64 nb, void
         hipLaunchKernelGGL((crt_combine_kernel<T, SET>), dim3(g2), dim3(256), 0, st, fd, (const u32 *)buf, n_fft, (T *)out, n_out, cc);
         if (hipGetLastError() != hipSuccess) rc = GFA_ERR_HIP;
     }
-    (void)gfa::scratch_free(buf, st);
     return rc;
 }
 
@@ -257,7 +257,8 @@ int run_planes(gfa_field *f, const void *a, i64 na, const void *b, i64 nb, void 
     int rc = aux_fields(1, aux); // set 1: P[0] = 469762049
     if (rc) return rc;
     u32 *buf = nullptr;
-    GFA_HIP(gfa::scratch_alloc((void **)&buf, sizeof(u32) * 2 * (size_t)nt * (size_t)n_fft, st));
+    Scratch ws(st);
+    GFA_HIP(ws.get(&buf, 2 * (size_t)nt * (size_t)n_fft));
     const int grid = (int)std::min<i64>((n_fft + 255) / 256, 256 * 16);
     if (bits) hipLaunchKernelGGL((planes_spread_kernel<T, true>), dim3(grid), dim3(256), 0, st, (const T *)a, na, (const T *)b, nb, buf, n_fft, nt, pm, df);
     else hipLaunchKernelGGL((planes_spread_kernel<T, false>), dim3(grid), dim3(256), 0, st, (const T *)a, na, (const T *)b, nb, buf, n_fft, nt, pm, df);
@@ -274,7 +275,6 @@ int run_planes(gfa_field *f, const void *a, i64 na, const void *b, i64 nb, void 
         else hipLaunchKernelGGL((planes_fold_kernel<T, false>), dim3(g3), dim3(256), 0, st, (const u32 *)buf, n_fft, (T *)out, n_out, bf, df);
         if (hipGetLastError() != hipSuccess) rc = GFA_ERR_HIP;
     }
-    (void)gfa::scratch_free(buf, st);
     return rc;
 }
 

@@ -149,8 +149,9 @@ int gfa_ntt_dist(gfa_field_t *f, void *nccl_comm, int rank, int world, const voi
     const int64_t csub = cols / nsub;
     SideSet *ss = nullptr;
     if (nsub > 1 && (rc = side_set(&ss))) return rc;
+    Scratch ws(st); // declared before any side-stream work: `work` goes back only after `st` has joined the side stream (below)
     char *work = nullptr;
-    GFA_HIP(gfa::scratch_alloc((void **)&work, 2 * bytes, st));
+    GFA_HIP(ws.get(&work, 2 * bytes));
     char *a = work, *recv = work + bytes;
     u64 omega_n2 = 0;
     HostArith::pow(f->calc, omega, n1, &omega_n2);
@@ -208,10 +209,7 @@ int gfa_ntt_dist(gfa_field_t *f, void *nccl_comm, int rank, int world, const voi
             if (!rc) rc = gfa_ntt(f, a, out_rows, n2, rows, omega_n2, 0, dtype, stream);
         }
     }
-    const hipError_t fe = gfa::scratch_free(work, st);
-    if (rc) return rc;
-    GFA_HIP(fe);
-    return GFA_OK;
+    return rc;
 }
 
 int gfa_intt_dist(gfa_field_t *f, void *nccl_comm, int rank, int world, const void *local_rows, void *out_cols, int64_t n1, int64_t n2,
@@ -226,8 +224,9 @@ int gfa_intt_dist(gfa_field_t *f, void *nccl_comm, int rank, int world, const vo
     u64 omega_inv = 0, w_rows = 0;
     if (!HostArith::inv(f->calc, omega, &omega_inv)) { set_error("gfa_intt_dist: omega is not invertible"); return GFA_ERR_INVALID; }
     HostArith::pow(f->calc, omega_inv, n1, &w_rows);
+    Scratch ws(st);
     char *work = nullptr;
-    GFA_HIP(gfa::scratch_alloc((void **)&work, 2 * bytes, st));
+    GFA_HIP(ws.get(&work, 2 * bytes));
     void *send = work, *recv = work + bytes;
     // (1) rows, written straight into the send buffer send[s][k1_local][c]; (2) the one exchange; (3) pre-twiddle + columns + 1/N
     rc = gfa_ntt_chunked(f, local_rows, send, n2, rows, w_rows, 0, 0, 0, 0, cols, rows * cols, cols, dtype, stream);
@@ -244,10 +243,7 @@ int gfa_intt_dist(gfa_field_t *f, void *nccl_comm, int rank, int world, const vo
     }
     if (!rc) rc = all_to_all(send, recv, (size_t)(rows * cols), dtype, nccl_comm, world, st);
     if (!rc) rc = gfa_ntt_columns_inv(f, recv, out_cols, n1, cols, (int64_t)rank * cols, n_total, omega_inv, scale_by_n_inverse, dtype, stream);
-    const hipError_t fe = gfa::scratch_free(work, st);
-    if (rc) return rc;
-    GFA_HIP(fe);
-    return GFA_OK;
+    return rc;
 }
 
 } // extern "C"

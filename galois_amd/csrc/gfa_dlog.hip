@@ -178,11 +178,11 @@ int ensure_plan_device(const gfa_field *f, Plan &pl, PlanDev **out)
             std::vector<u32> idxs(m);
             for (u64 j = 0; j < m; j++) { vals[j] = baby[j].first; idxs[j] = baby[j].second; }
             u64 *dv; u32 *di;
-            GFA_HIP(hipMalloc((void **)&dv, sizeof(u64) * m));
-            GFA_HIP(hipMalloc((void **)&di, sizeof(u32) * m));
-            GFA_HIP(hipMemcpy(dv, vals.data(), sizeof(u64) * m, hipMemcpyHostToDevice));
-            GFA_HIP(hipMemcpy(di, idxs.data(), sizeof(u32) * m, hipMemcpyHostToDevice));
-            pd.allocs.push_back(dv); pd.allocs.push_back(di);
+            int rc;
+            if ((rc = device_upload(&dv, vals))) return rc;
+            pd.allocs.push_back(dv);
+            if ((rc = device_upload(&di, idxs))) return rc;
+            pd.allocs.push_back(di);
             fc.baby_val = dv; fc.baby_idx = di;
         }
         pd.ready = true;
@@ -238,13 +238,13 @@ int dlog_run(gfa_field *f, const void *a, i64 sa, const void *base, i64 sb, int6
     if (rc || !base) return rc;
     const i64 nb = sb ? n : 1;
     u64 *lb = nullptr;
-    GFA_HIP(gfa::scratch_alloc((void **)&lb, sizeof(u64) * (size_t)nb, st));
+    Scratch ws(st);
+    GFA_HIP(ws.get(&lb, (size_t)nb));
     rc = dispatch_dlog(f->calc, dtype, *pd, base, sb, lb, nb, st, err);
     if (!rc) {
         const unsigned blocks = (unsigned)std::max<i64>(1, std::min<i64>((n + 255) / 256, 65535));
         hipLaunchKernelGGL(dlog_rebase_kernel, dim3(blocks), dim3(256), 0, st, (u64 *)out, lb, (int)sb, pd->N, n, err);
     }
-    GFA_HIP(gfa::scratch_free(lb, st));
     return rc;
 }
 

@@ -1024,12 +1024,12 @@ static int launch_tab8_claim(int grid, const uint8_t *table, const void *a, cons
     // The counter is this launch's own (stream-ordered allocation) and its reset is a node of the same stream, so concurrent
     // streams share nothing and a captured graph resets it on every replay.
     unsigned int *counter = nullptr;
-    GFA_HIP(gfa::scratch_alloc((void **)&counter, sizeof(unsigned int), st));
+    Scratch ws(st);
+    GFA_HIP(ws.get(&counter, 1));
     GFA_HIP(hipMemsetAsync(counter, 0, sizeof(unsigned int), st));
     hipLaunchKernelGGL(k, dim3(grid), dim3(TAB8_THREADS), 65536, st, table, (const uint8_t *)a, (const uint8_t *)b, (uint8_t *)out,
                        n, err, counter);
     GFA_HIP(hipGetLastError());
-    GFA_HIP(gfa::scratch_free(counter, st));
     return GFA_OK;
 }
 

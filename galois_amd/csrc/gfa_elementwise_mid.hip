@@ -739,14 +739,13 @@ int big16_inv_launch(const MidDesc &d, const FieldDev &lut, const void *a, i64 s
     const i64 blocks = (nvec + T - 1) / T;
     const int cus = num_cus();
     if (MODE == 3) { // the per-call power table: qa entries of stream-ordered scratch
+        Scratch ws(st);
         u16 *tab = nullptr;
-        if (gfa::scratch_alloc((void **)&tab, (size_t)d.qa * sizeof(u16), st) != hipSuccess) { (void)hipGetLastError(); return GFA_ERR_UNSUPPORTED; }
+        if (ws.get(&tab, (size_t)d.qa) != hipSuccess) { (void)hipGetLastError(); return GFA_ERR_UNSUPPORTED; }
         hipLaunchKernelGGL(big16_pow_table_kernel, dim3((int)(d.qa / 256u)), dim3(256), 0, st, d, tab);
         hipLaunchKernelGGL(k, dim3((int)(blocks < cus ? blocks : cus)), dim3(T), lds, st, d, (const u16 *)tab, 0u, 0u, (u64)0, (const u16 *)nullptr, 0, (const u16 *)b, 1,
                            (u16 *)out, nvec, err);
-        const hipError_t le = hipGetLastError();
-        GFA_HIP(gfa::scratch_free(tab, st));
-        GFA_HIP(le);
+        GFA_HIP(hipGetLastError());
         return GFA_OK;
     }
     hipLaunchKernelGGL(k, dim3((int)(blocks < cus ? blocks : cus)), dim3(T), lds, st, d, d.image + 3 * (size_t)d.qa, (u32)lut.p, (u32)(0x100000000ull / lut.p), (u64)lut.irr,
@@ -827,17 +826,16 @@ int big16_launch(const MidDesc &d, const void *a, i64 sa, const void *b, i64 sb,
         // array is walked in slices of 2^26 elements (a 128 MiB index slice) that share ONE work buffer: a multi-GB operand
         // costs no more scratch than a small one.  Without a work buffer the fused kernel below does the job.
         const i64 slice = std::min<i64>(nvec, (i64)1 << 23);
+        Scratch ws(st);
         u16 *idx = nullptr;
-        if (gfa::scratch_alloc((void **)&idx, (size_t)slice * 16, st) == hipSuccess) {
+        if (ws.get(&idx, (size_t)slice * 8) == hipSuccess) {
             for (i64 v0 = 0; v0 < nvec; v0 += slice) {
                 const i64 cnt = std::min<i64>(slice, nvec - v0);
                 hipLaunchKernelGGL(ka, dim3(cus), dim3(T), lds, st, d, (const u16 *)a + (sa ? v0 * 8 : 0), (int)sa, (const u16 *)b + (sb ? v0 * 8 : 0),
                                    (int)sb, idx, cnt, err);
                 hipLaunchKernelGGL(kb, dim3(cus), dim3(T), lds, st, d, (const u16 *)idx, (u16 *)out + v0 * 8, cnt);
             }
-            const hipError_t le = hipGetLastError();
-            GFA_HIP(gfa::scratch_free(idx, st));
-            GFA_HIP(le);
+            GFA_HIP(hipGetLastError());
             return GFA_OK;
         }
         (void)hipGetLastError(); // allocation failed: clear the sticky error and take the fused kernel, which needs no scratch
@@ -1017,16 +1015,15 @@ int big16_power_each(const FieldDev &lut, const void *image, const void *a, cons
     const i64 nvec = n >> 3;
     const int cus = num_cus();
     const i64 slice = std::min<i64>(nvec, (i64)1 << 23); // index slices of at most 128 MiB: they stay in the Infinity Cache between the two kernels
+    Scratch ws(st);
     u16 *idx = nullptr;
-    if (gfa::scratch_alloc((void **)&idx, (size_t)slice * 16, st) != hipSuccess) { (void)hipGetLastError(); return GFA_ERR_UNSUPPORTED; }
+    if (ws.get(&idx, (size_t)slice * 8) != hipSuccess) { (void)hipGetLastError(); return GFA_ERR_UNSUPPORTED; }
     for (i64 v0 = 0; v0 < nvec; v0 += slice) {
         const i64 cnt = std::min<i64>(slice, nvec - v0);
         hipLaunchKernelGGL(ka, dim3(cus), dim3(T), lds, st, d, (const u16 *)a + v0 * 8, e + v0 * 8, idx, cnt, err);
         hipLaunchKernelGGL(kb, dim3(cus), dim3(T), lds, st, d, (const u16 *)idx, (u16 *)out + v0 * 8, cnt);
     }
-    const hipError_t le = hipGetLastError();
-    GFA_HIP(gfa::scratch_free(idx, st));
-    GFA_HIP(le);
+    GFA_HIP(hipGetLastError());
     return GFA_OK;
 }
 
@@ -1059,7 +1056,8 @@ int big16_run_wide_t(const FieldDev &lut, const void *image, int op, const T *a,
     if (n8 == 0) return GFA_OK;
     const i64 na = sa ? n8 : 8, nb = b ? (sb ? n8 : 8) : 0;
     u16 *wa = nullptr, *wb = nullptr, *wo = nullptr;
-    if (gfa::scratch_alloc((void **)&wa, sizeof(u16) * (size_t)(na + nb + n8) + 64, st) != hipSuccess) {
+    Scratch ws(st);
+    if (ws.get(&wa, (size_t)(na + nb + n8) + 32) != hipSuccess) {
         (void)hipGetLastError();
         return GFA_ERR_UNSUPPORTED; // no work buffer: the generic kernels take the call
     }
@@ -1077,7 +1075,6 @@ int big16_run_wide_t(const FieldDev &lut, const void *image, int op, const T *a,
         hipLaunchKernelGGL((widen16_kernel<T>), dim3(grid), dim3(256), 0, st, (const u16 *)wo, out, n8);
         if (hipGetLastError() != hipSuccess) rc = GFA_ERR_HIP;
     }
-    (void)gfa::scratch_free(wa, st);
     return rc;
 }
 

@@ -345,8 +345,8 @@ int get_dev(const FieldDev &c, PackedDev *out)
         if (!make_plan(c.p, c.m, &d.pl)) return GFA_ERR_UNSUPPORTED;
         std::vector<pu32> t;
         build_tables(d.pl, t);
-        GFA_HIP(hipMalloc((void **)&d.tab, sizeof(pu32) * t.size()));
-        GFA_HIP(hipMemcpy(d.tab, t.data(), sizeof(pu32) * t.size(), hipMemcpyHostToDevice)); // synchronous: usable from any stream afterwards
+        const int rc = device_upload(&d.tab, t); // synchronous: usable from any stream afterwards
+        if (rc) return rc;
         it = g_pk.emplace(key, d).first;
     }
     *out = it->second;
@@ -371,8 +371,8 @@ int get_dev2(const FieldDev &c, Packed2Dev *out)
         if (!make_plan2(c.p, c.m, &d.pl)) return GFA_ERR_UNSUPPORTED;
         std::vector<pu32> t;
         build_tables2(d.pl, t);
-        GFA_HIP(hipMalloc((void **)&d.tab, sizeof(pu32) * t.size()));
-        GFA_HIP(hipMemcpy(d.tab, t.data(), sizeof(pu32) * t.size(), hipMemcpyHostToDevice));
+        const int rc = device_upload(&d.tab, t);
+        if (rc) return rc;
         it = g_pk2.emplace(key, d).first;
     }
     *out = it->second;
@@ -588,8 +588,8 @@ int packed_divn_run(const FieldDev &c, int dtype, const void *a, i64 sa, const v
                 t.swap(h);
             }
             pu32 *d = nullptr;
-            GFA_HIP(hipMalloc((void **)&d, sizeof(pu32) * t.size()));
-            GFA_HIP(hipMemcpy(d, t.data(), sizeof(pu32) * t.size(), hipMemcpyHostToDevice));
+            const int rc = device_upload(&d, t);
+            if (rc) return rc;
             it = g_inv_tab.emplace(key, d).first;
         }
         inv = it->second;
@@ -613,14 +613,13 @@ int pow24_run(const u32 *exp_tab, const u32 *log_tab, u64 q, const void *a, cons
 {
     if (!exp_tab || !log_tab || q <= 65536 || q > ((u64)1 << 20) || n < 8 * (i64)q || !al16p(out) || !al16p(a)) return GFA_ERR_UNSUPPORTED;
     uint8_t *tab = nullptr;
-    if (scratch_alloc((void **)&tab, 3 * (size_t)q + 4, st) != hipSuccess) { (void)hipGetLastError(); return GFA_ERR_UNSUPPORTED; }
+    Scratch ws(st);
+    if (ws.get(&tab, 3 * (size_t)q + 4) != hipSuccess) { (void)hipGetLastError(); return GFA_ERR_UNSUPPORTED; }
     hipLaunchKernelGGL(pow24_table_kernel, dim3((int)((q + 255) / 256)), dim3(256), 0, st, exp_tab, log_tab, (u32)q, e_ptr, tab);
     const i64 blocks = std::max<i64>(1, (n / 4 + PK_THREADS - 1) / PK_THREADS);
     hipLaunchKernelGGL((packed_divt_kernel<4, true>), dim3((int)std::min<i64>(blocks, (i64)num_cus() * 4)), dim3(PK_THREADS), 0, st, Plan{}, MulAux{},
                        (const pu32 *)nullptr, (const uint8_t *)tab, (const uint32_t *)nullptr, 0, (const uint32_t *)a, 1, (uint32_t *)out, n, dev_err, e_ptr);
-    const hipError_t le = hipGetLastError();
-    GFA_HIP(scratch_free(tab, st));
-    GFA_HIP(le);
+    GFA_HIP(hipGetLastError());
     return GFA_OK;
 }
 

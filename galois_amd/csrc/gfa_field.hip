@@ -62,6 +62,17 @@ hipError_t scratch_alloc(void **p, size_t bytes, hipStream_t st)
 
 hipError_t scratch_free(void *p, hipStream_t st) { return hipFreeAsync(p, st); }
 
+int device_upload(void **out, const void *host, size_t bytes)
+{
+    *out = nullptr;
+    GFA_HIP(hipMalloc(out, std::max<size_t>(bytes, 16)));
+    const hipError_t e = bytes > 0 ? hipMemcpy(*out, host, bytes, hipMemcpyHostToDevice) : hipSuccess;
+    if (e == hipSuccess) return GFA_OK;
+    (void)hipFree(*out);
+    *out = nullptr;
+    return hip_fail(e, "hipMemcpy of a device table");
+}
+
 int num_cus()
 {
     static int cached[64] = {0};
@@ -231,10 +242,8 @@ gfa::FieldDev gfa_field::lut_desc(const gfa::FieldDeviceState &st) const
 template <typename T>
 static int upload(T **dst, const std::vector<T> &src)
 {
-    if (src.empty()) { *dst = nullptr; return GFA_OK; }
-    GFA_HIP(hipMalloc((void **)dst, src.size() * sizeof(T)));
-    GFA_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-    return GFA_OK;
+    if (src.empty()) { *dst = nullptr; return GFA_OK; } // an absent table stays a null pointer: kernels may test for it
+    return device_upload(dst, src);
 }
 
 int gfa_field::ensure_device(int *device_out, gfa::FieldDeviceState **st_out)
@@ -320,6 +329,20 @@ int gfa_device_count(void)
 }
 
 int gfa_trim_scratch(uint64_t keep_bytes) { return scratch_trim((size_t)keep_bytes); }
+
+int64_t gfa_debug_scratch_in_use(void)
+{
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return -1;
+    hipMemPool_t pool = nullptr;
+    {
+        std::lock_guard<std::mutex> lock(g_pool_mu);
+        if (dev < (int)g_pools.size()) pool = g_pools[dev];
+    }
+    uint64_t used = 0;
+    if (!pool || hipMemPoolGetAttribute(pool, hipMemPoolAttrUsedMemCurrent, &used) != hipSuccess) return -1;
+    return (int64_t)used;
+}
 
 int gfa_field_create(uint64_t p, uint32_t m, const uint64_t *irr, uint64_t alpha, gfa_field_t **out)
 {

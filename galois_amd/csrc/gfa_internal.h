@@ -10,6 +10,7 @@
 
 #include "../../include/galois_amd.h"
 #include "gfa_arith.h"
+#include "gfa_scratch.h"
 
 struct gfa_field;
 
@@ -26,13 +27,16 @@ int time_loop(hipStream_t st, int iters, float *ms_out, const std::function<int(
         if (_e != hipSuccess) return gfa::hip_fail(_e, #call); \
     } while (0)
 
-// Stream-ordered work buffers of one call (hipMallocFromPoolAsync / hipFreeAsync) from a pool the library owns, one per
-// device, with a release threshold of 256 MiB (GFA_SCRATCH_KEEP_MB): freed blocks up to that total stay in the pool across
-// synchronisations instead of going back to the driver (the device's default pool releases at every synchronisation --
-// 0.05 ms per Reed-Solomon decode); gfa_trim_scratch() returns the rest on demand.
-hipError_t scratch_alloc(void **p, size_t bytes, hipStream_t st);
-hipError_t scratch_free(void *p, hipStream_t st);
 int scratch_trim(size_t keep_bytes); // synchronises the device, returns unused pool memory beyond keep_bytes to the driver
+
+// A persistent device table: hipMalloc of max(bytes, 16) -- never a null pointer, also for an empty table -- and a
+// synchronous copy of `bytes` from the host.  A failed copy frees the allocation and leaves *out null.
+int device_upload(void **out, const void *host, size_t bytes);
+template <class T>
+inline int device_upload(T **out, const std::vector<T> &host)
+{
+    return device_upload((void **)out, host.data(), host.size() * sizeof(T));
+}
 
 // compute units of the current device, cached per device (256 when the query fails)
 int num_cus();

@@ -34,26 +34,6 @@ inline int mfma_bits_min_log()
     return v;
 }
 
-// stream-ordered work buffers of one call, released on EVERY way out of it (a failed launch in the middle used to leave them in the pool's books)
-struct Scratch {
-    hipStream_t st;
-    void *p[4] = {nullptr, nullptr, nullptr, nullptr};
-    int n = 0;
-    explicit Scratch(hipStream_t s) : st(s) {}
-    Scratch(const Scratch &) = delete;
-    Scratch &operator=(const Scratch &) = delete;
-    hipError_t get(void **out, size_t bytes)
-    {
-        const hipError_t e = gfa::scratch_alloc(out, bytes, st);
-        if (e == hipSuccess) p[n++] = *out;
-        return e;
-    }
-    ~Scratch()
-    {
-        for (int i = 0; i < n; i++) (void)gfa::scratch_free(p[i], st);
-    }
-};
-
 __device__ __forceinline__ int8_t centre(u32 a, u32 p, u32 half) { return (int8_t)(a > half ? (int)a - (int)p : (int)a); }
 // operand byte: the centred residue (shift < 0, p <= 256) or the 7-bit limb of the element at bit `shift` (larger primes)
 __device__ __forceinline__ int8_t operand(u64 a, u32 p, u32 half, int shift)
@@ -219,8 +199,8 @@ int run_mfma(const FieldDev &fd, const void *a, const void *b, void *out, i64 ba
     const i64 nA = a_bstride ? batch : 1, nB = b_bstride ? batch : 1;
     int8_t *Ac = nullptr, *Bc = nullptr;
     Scratch ws(st);
-    GFA_HIP(ws.get((void **)&Ac, (size_t)(nA * Mp * Kp)));
-    GFA_HIP(ws.get((void **)&Bc, (size_t)(nB * Np * Kp)));
+    GFA_HIP(ws.get(&Ac, (size_t)(nA * Mp * Kp)));
+    GFA_HIP(ws.get(&Bc, (size_t)(nB * Np * Kp)));
     const u32 p = (u32)fd.p;
     {
         const i64 total = Mp * Kp;
@@ -266,9 +246,9 @@ int run_mfma_limbs(const FieldDev &fd, int nl, const void *a, const void *b, voi
     int8_t *Ac = nullptr, *Bc = nullptr;
     int *D = nullptr;
     Scratch ws(st);
-    GFA_HIP(ws.get((void **)&Ac, (size_t)(nl * Mp * Kp)));
-    GFA_HIP(ws.get((void **)&Bc, (size_t)(nl * Np * Kp)));
-    GFA_HIP(ws.get((void **)&D, sizeof(int) * (size_t)(ndiag * plane)));
+    GFA_HIP(ws.get(&Ac, (size_t)(nl * Mp * Kp)));
+    GFA_HIP(ws.get(&Bc, (size_t)(nl * Np * Kp)));
+    GFA_HIP(ws.get(&D, (size_t)(ndiag * plane)));
     const u32 p32 = (u32)(fd.p & 0xffffffffu);
     static const int itemsize[4] = {1, 2, 4, 8};
     (void)itemsize;
@@ -376,9 +356,9 @@ int run_mfma_bits(const FieldDev &fd, const void *a, const void *b, void *out, i
     int8_t *Ac = nullptr, *Bc = nullptr;
     uint8_t *P = nullptr;
     Scratch ws(st);
-    GFA_HIP(ws.get((void **)&Ac, (size_t)(nt * Mp * Kp)));
-    GFA_HIP(ws.get((void **)&Bc, (size_t)(nt * Np * Kp)));
-    GFA_HIP(ws.get((void **)&P, (size_t)(nt * plane)));
+    GFA_HIP(ws.get(&Ac, (size_t)(nt * Mp * Kp)));
+    GFA_HIP(ws.get(&Bc, (size_t)(nt * Np * Kp)));
+    GFA_HIP(ws.get(&P, (size_t)(nt * plane)));
     for (i64 bi = 0; bi < batch; bi++) { // one matrix pair at a time: nt planes of each operand are the large scratch
         const T *pa = (const T *)a + bi * a_bstride;
         const T *pb = (const T *)b + bi * b_bstride;
@@ -484,9 +464,9 @@ int run_mfma_digits(const FieldDev &fd, const void *a, const void *b, void *out,
     int8_t *Ac = nullptr, *Bc = nullptr;
     uint8_t *P = nullptr;
     Scratch ws(st);
-    GFA_HIP(ws.get((void **)&Ac, (size_t)(nt * Mp * Kp)));
-    GFA_HIP(ws.get((void **)&Bc, (size_t)(nt * Np * Kp)));
-    GFA_HIP(ws.get((void **)&P, (size_t)(nt * plane)));
+    GFA_HIP(ws.get(&Ac, (size_t)(nt * Mp * Kp)));
+    GFA_HIP(ws.get(&Bc, (size_t)(nt * Np * Kp)));
+    GFA_HIP(ws.get(&P, (size_t)(nt * plane)));
     for (i64 bi = 0; bi < batch; bi++) {
         const T *pa = (const T *)a + bi * a_bstride;
         const T *pb = (const T *)b + bi * b_bstride;

@@ -1016,12 +1016,12 @@ struct Plan {
     // generic path
     void *wpow = nullptr; // n entries
     std::vector<i64> factors;
-    struct Scratch *sc = nullptr; // work buffers of the (device, stream) this call runs on; set at lookup
+    struct PlanScratch *sc = nullptr; // work buffers of the (device, stream) this call runs on; set at lookup
 };
 
 // Work buffers (inter-pass intermediates, dtype conversion) are shared by every plan used on one (device, stream): they are
 // grow-only, so their size is the largest transform seen on that stream rather than the sum over all cached plans.
-struct Scratch {
+struct PlanScratch {
     DevBuf ws0, ws1, cvt;
 };
 
@@ -1036,7 +1036,7 @@ struct PlanKey {
 
 std::mutex g_plan_mu;
 std::map<PlanKey, Plan *> g_plans;
-std::map<std::pair<int, hipStream_t>, Scratch *> g_scratch;
+std::map<std::pair<int, hipStream_t>, PlanScratch *> g_scratch;
 
 // under g_plan_mu
 Plan *lookup_plan(const PlanKey &key, hipStream_t st)
@@ -1045,7 +1045,7 @@ Plan *lookup_plan(const PlanKey &key, hipStream_t st)
     if (it == g_plans.end()) it = g_plans.emplace(key, new Plan()).first;
     auto sk = std::make_pair(key.device, st);
     auto is = g_scratch.find(sk);
-    if (is == g_scratch.end()) is = g_scratch.emplace(sk, new Scratch()).first;
+    if (is == g_scratch.end()) is = g_scratch.emplace(sk, new PlanScratch()).first;
     it->second->sc = is->second;
     return it->second;
 }

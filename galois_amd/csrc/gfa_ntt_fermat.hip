@@ -423,10 +423,8 @@ int ntt_fermat16(const void *in, void *out, i64 batch, u64 omega, int negate, hi
             }
             for (u32 k1 = 0; k1 < 32; k1++)
                 for (u32 r = 0; r < 32; r++) t2[k1 * 32 + r] = balanced(pw[((u32)r0 * r * k1) & nmask]); // the 1024-point sub-transform's root is w^R0
-            GFA_HIP(hipMalloc((void **)&p.tw1, t1.size() * sizeof(int)));
-            GFA_HIP(hipMalloc((void **)&p.tw2, t2.size() * sizeof(int)));
-            GFA_HIP(hipMemcpy(p.tw1, t1.data(), t1.size() * sizeof(int), hipMemcpyHostToDevice));
-            GFA_HIP(hipMemcpy(p.tw2, t2.data(), t2.size() * sizeof(int), hipMemcpyHostToDevice));
+            int rc;
+            if ((rc = device_upload(&p.tw1, t1)) || (rc = device_upload(&p.tw2, t2))) return rc;
             hipDeviceProp_t prop;
             GFA_HIP(hipGetDeviceProperties(&prop, dev));
             p.u = u; p.uinv = uinv; p.cus = prop.multiProcessorCount; p.logg = logg; p.ok = true;

@@ -607,13 +607,6 @@ void free_plan(M32Plan *pl)
     delete pl;
 }
 
-int upload(const std::vector<i32> &h, i32 **d)
-{
-    GFA_HIP(hipMalloc((void **)d, sizeof(i32) * h.size()));
-    GFA_HIP(hipMemcpy(*d, h.data(), sizeof(i32) * h.size(), hipMemcpyHostToDevice));
-    return GFA_OK;
-}
-
 // pairs (Montgomery form of w^e, companion) for e < count, w = omega^mult
 int pair_table(u64 p, u32 pinv, u64 omega, u64 mult, int count, i32 **d)
 {
@@ -626,7 +619,7 @@ int pair_table(u64 p, u32 pinv, u64 omega, u64 mult, int count, i32 **d)
         h[2 * e + 1] = (i32)((u32)wm * pinv);
         cur = cur * w % p;
     }
-    return upload(h, d);
+    return device_upload(d, h);
 }
 
 constexpr int split_log1(int logL) { return (logL + 1) / 2; } // R1 >= R2
@@ -686,7 +679,7 @@ int build_plan(M32Plan *pl, u64 p, i64 n, u64 omega, int split, hipStream_t st)
                 cur = cur * w % p;
             }
         }
-        if ((rc = upload(h, net_a))) return rc;
+        if ((rc = device_upload(net_a, h))) return rc;
         return pair_table(p, pinv, omega, wl_mult, (int)Lh, mid);
     };
     if (logn >= 11 && logn <= 16) {
@@ -700,7 +693,7 @@ int build_plan(M32Plan *pl, u64 p, i64 n, u64 omega, int split, hipStream_t st)
                 h.push_back((i32)((u32)wm * pinv));
                 cur = cur * w % p;
             }
-            return upload(h, d);
+            return device_upload(d, h);
         };
         if ((rc = pairs(powmod(omega, 1024, p), std::max(R0 / 2, 1), &pl->one_net0))) return rc;       // w_R0 = w_n^1024
         if ((rc = pairs(powmod(omega, (u64)R0 * 32, p), 16, &pl->one_net1))) return rc;                // w_32 = w_1024^32, w_1024 = w_n^R0
@@ -708,7 +701,7 @@ int build_plan(M32Plan *pl, u64 p, i64 n, u64 omega, int split, hipStream_t st)
         std::vector<i32> hw(1024);
         u64 cur = 1;
         for (int j = 0; j < 1024; j++) { hw[j] = mont_centred(cur, p); cur = cur * omega % p; }          // w_n^j
-        if ((rc = upload(hw, &pl->one_wj))) return rc;
+        if ((rc = device_upload(&pl->one_wj, hw))) return rc;
     }
     if ((rc = line_tables(pl->log1, &pl->net1, &pl->mid1))) return rc;
     if (pl->log3) {

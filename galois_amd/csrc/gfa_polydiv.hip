@@ -177,15 +177,6 @@ __global__ __launch_bounds__(MaxThreads<F>::most) void pd_powmod_kernel(FieldDev
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------
-struct Scratch { // a work buffer of the call: returned to the pool on every way out
-    void *p = nullptr;
-    hipStream_t st;
-    explicit Scratch(hipStream_t s) : st(s) {}
-    ~Scratch() { if (p) (void)gfa::scratch_free(p, st); }
-    Scratch(const Scratch &) = delete;
-    Scratch &operator=(const Scratch &) = delete;
-};
-
 int round_up_threads(int work, int most)
 {
     const int t = (std::max(work, 1) + 63) / 64 * 64;
@@ -212,8 +203,9 @@ int launch_div(const FieldDev &fd, const DivJob &j)
         return GFA_OK;
     }
     Scratch ws(j.st);
-    GFA_HIP(gfa::scratch_alloc(&ws.p, sizeof(E) * ((size_t)j.batch * (size_t)j.na + (size_t)j.nb), j.st));
-    E *bw = (E *)ws.p, *rows = bw + j.nb;
+    E *bw = nullptr;
+    GFA_HIP(ws.get(&bw, (size_t)j.batch * (size_t)j.na + (size_t)j.nb));
+    E *rows = bw + j.nb;
     hipLaunchKernelGGL((pd_widen_kernel<E>), dim3((unsigned)std::min(256, (j.nb + 255) / 256)), dim3(256), 0, j.st, j.b, j.dtype, bw, j.nb);
     GFA_HIP(hipGetLastError());
     hipLaunchKernelGGL((pd_divmod_global_kernel<F>), dim3((unsigned)j.batch), dim3(threads), 0, j.st, fd, j.a, j.na, (const E *)bw, j.nb, rows, j.q, j.r, j.dtype);
@@ -330,11 +322,12 @@ int gfa_poly_powmod(gfa_field_t *f, const void *a, int64_t batch, int64_t na, co
     if (rc) return rc;
     const FieldDev fd = f->use_lookup() ? f->lut_desc(*ds) : f->calc;
     hipStream_t st = (hipStream_t)stream;
-    Scratch ebuf(st);
-    GFA_HIP(gfa::scratch_alloc(&ebuf.p, sizeof(u64) * (size_t)n_limbs, st));
-    rc = upload(exp_limbs, (size_t)n_limbs, (u64 *)ebuf.p, st);
+    Scratch ws(st);
+    u64 *exps = nullptr;
+    GFA_HIP(ws.get(&exps, (size_t)n_limbs));
+    rc = upload(exp_limbs, (size_t)n_limbs, exps, st);
     if (rc) return rc;
-    const PowJob j{a, c, batch, (int)na, (int)nc, dtype, (const u64 *)ebuf.p, (int)n_limbs, out, st};
+    const PowJob j{a, c, batch, (int)na, (int)nc, dtype, exps, (int)n_limbs, out, st};
     return dispatch_pow(fd, dtype, j);
 }
 

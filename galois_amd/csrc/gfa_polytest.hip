@@ -271,16 +271,6 @@ std::vector<int> rabin_steps(int m)
     return out;
 }
 
-// a work buffer of the call: returned to the pool on every way out
-struct Scratch {
-    void *p = nullptr;
-    hipStream_t st;
-    explicit Scratch(hipStream_t s) : st(s) {}
-    ~Scratch() { if (p) (void)gfa::scratch_free(p, st); }
-    Scratch(const Scratch &) = delete;
-    Scratch &operator=(const Scratch &) = delete;
-};
-
 int upload(const std::vector<u64> &h, u64 *d, hipStream_t st)
 {
     for (size_t off = 0; off < h.size(); off += PT_ARG_WORDS) {
@@ -339,16 +329,16 @@ int gfa_poly_classify(gfa_field_t *f, const void *coeffs, int64_t batch, int64_t
     host.insert(host.end(), cofactor_exps, cofactor_exps + (size_t)(n_exps * exp_limbs));
     j.want_primitive = n_exps > 0 || cofactor_exps != nullptr;
 
-    Scratch dev_buf(st), list_buf(st);
-    GFA_HIP(gfa::scratch_alloc(&dev_buf.p, sizeof(u64) * host.size(), st));
-    u64 *dev = (u64 *)dev_buf.p;
+    Scratch ws(st);
+    u64 *dev = nullptr;
+    i64 *list = nullptr;
+    GFA_HIP(ws.get(&dev, host.size()));
     rc = upload(host, dev, st);
     if (rc) return rc;
     if (j.want_primitive) { // list[0] is the count, the indices follow
-        GFA_HIP(gfa::scratch_alloc(&list_buf.p, sizeof(i64) * (size_t)(batch + 1), st));
-        GFA_HIP(hipMemsetAsync(list_buf.p, 0, sizeof(i64), st));
+        GFA_HIP(ws.get(&list, (size_t)(batch + 1)));
+        GFA_HIP(hipMemsetAsync(list, 0, sizeof(i64), st));
     }
-    i64 *list = (i64 *)list_buf.p;
     {
         j.coeffs = coeffs; j.batch = batch; j.m = m; j.dtype = dtype;
         j.sched = dev; j.exps = dev + exps_at; j.n_exps = (int)n_exps; j.exp_limbs = (int)exp_limbs;

@@ -1660,9 +1660,7 @@ int gfa_rs::ensure_device(int *device_out, Dev **out)
         auto upload = [](const std::vector<uint64_t> &src, uint32_t **dst) -> int {
             std::vector<uint32_t> w(src.size());
             for (size_t i = 0; i < w.size(); i++) w[i] = (uint32_t)src[i];
-            GFA_HIP(hipMalloc((void **)dst, std::max<size_t>(w.size() * sizeof(uint32_t), 16)));
-            if (!w.empty()) GFA_HIP(hipMemcpy(*dst, w.data(), w.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-            return GFA_OK;
+            return device_upload(dst, w);
         };
         int rc;
         if ((rc = upload(P, &st.Pw)) || (rc = upload(roots, &st.rootsw)) || (rc = upload(gpoly, &st.gw))) return rc;
@@ -1673,25 +1671,20 @@ int gfa_rs::ensure_device(int *device_out, Dev **out)
         std::vector<uint8_t> P8((size_t)k * nk), r8(roots.size());
         for (size_t i = 0; i < P8.size(); i++) P8[i] = (uint8_t)P[i];
         for (size_t i = 0; i < r8.size(); i++) r8[i] = (uint8_t)roots[i];
-        GFA_HIP(hipMalloc((void **)&st.P8, std::max<size_t>(P8.size(), 16)));
-        GFA_HIP(hipMalloc((void **)&st.roots8, std::max<size_t>(r8.size(), 16)));
-        if (!P8.empty()) GFA_HIP(hipMemcpy(st.P8, P8.data(), P8.size(), hipMemcpyHostToDevice));
-        if (!r8.empty()) GFA_HIP(hipMemcpy(st.roots8, r8.data(), r8.size(), hipMemcpyHostToDevice));
+        int rc;
+        if ((rc = device_upload(&st.P8, P8)) || (rc = device_upload(&st.roots8, r8))) return rc;
         {
             std::vector<uint8_t> g8(gpoly.size());
             for (size_t i = 0; i < g8.size(); i++) g8[i] = (uint8_t)gpoly[i];
-            GFA_HIP(hipMalloc((void **)&st.g8, std::max<size_t>(g8.size(), 16)));
-            GFA_HIP(hipMemcpy(st.g8, g8.data(), g8.size(), hipMemcpyHostToDevice));
+            if ((rc = device_upload(&st.g8, g8))) return rc;
         }
         if (field->has_tab8 && field->calc.p == 2 && nk >= 4 && nk <= 64 && nk % 4 == 0) {
             // tables built by gfa_rs_host.h (checked on the host by tests/csrc/rs_host_test.cpp): the LFSR rows in the order
             // rs_lfsr_kernel reads them, and the lane tables of rs_decode_bin_kernel
             const std::vector<uint32_t> rows = rs_lfsr_rows(field->h_mul8.data(), field->calc.q, gpoly, nk);
-            GFA_HIP(hipMalloc((void **)&st.lfsr, rows.size() * sizeof(uint32_t)));
-            GFA_HIP(hipMemcpy(st.lfsr, rows.data(), rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+            if ((rc = device_upload(&st.lfsr, rows))) return rc;
             const std::vector<uint8_t> aux = rs_decode_lane_tables(field->h_mul8.data(), field->calc.q, alpha, n, roots);
-            GFA_HIP(hipMalloc((void **)&st.aux8, aux.size()));
-            GFA_HIP(hipMemcpy(st.aux8, aux.data(), aux.size(), hipMemcpyHostToDevice));
+            if ((rc = device_upload(&st.aux8, aux))) return rc;
         }
         st.ready = true;
     }
@@ -1968,13 +1961,12 @@ int gfa_rs_decode(gfa_rs_t *code, const void *recv, const uint8_t *erasures, int
             const size_t need = (size_t)batch * nk;
             // remainder scratch of THIS call, stream-ordered (two decodes of one code on different streams, or from
             // different host threads, must not share it; no device synchronisation, so the call stays graph-capturable)
+            Scratch ws(st);
             uint8_t *rem = nullptr;
-            GFA_HIP(gfa::scratch_alloc((void **)&rem, need, st));
+            GFA_HIP(ws.get(&rem, need));
             if ((rc = launch_lfsr<false>(code, cd, (const uint8_t *)recv, erasures, (int)ns, (uint8_t *)out_codeword, 0, rem, nullptr,
-                                         batch, st))) {
-                (void)gfa::scratch_free(rem, st);
+                                         batch, st)))
                 return rc;
-            }
             const RsParams rp = make_params(code);
             const size_t fixed = 65536 + 1280;
             const bool small = (int)code->roots.size() + 4 <= 40;
@@ -1993,10 +1985,7 @@ int gfa_rs_decode(gfa_rs_t *code, const void *recv, const uint8_t *erasures, int
 #define GFA_K2(SV, W, IDX)                                                                                              \
     do {                                                                                                                \
         static bool attr = false;                                                                                       \
-        if (!attr && (rc = decode_lds_base_is_zero(rs_decode_bin_kernel<SV, W>))) {                                     \
-            (void)gfa::scratch_free(rem, st);                                                                           \
-            return rc;                                                                                                  \
-        }                                                                                                               \
+        if (!attr && (rc = decode_lds_base_is_zero(rs_decode_bin_kernel<SV, W>))) return rc;                            \
         if ((rc = set_lds_limit(rs_decode_bin_kernel<SV, W>, &attr))) return rc;                                        \
         hipLaunchKernelGGL((rs_decode_bin_kernel<SV, W>), dim3(grid), dim3(nwaves * 64), lds, st, make_tables(*ds), rpk, \
                            erasures, rem, cd->aux8, (int)ns, (uint8_t *)out_codeword, (i64 *)out_n_errors, batch);      \
@@ -2017,9 +2006,7 @@ int gfa_rs_decode(gfa_rs_t *code, const void *recv, const uint8_t *erasures, int
                 }
             }
 #undef GFA_K2
-            const hipError_t launch_err = hipGetLastError();
-            GFA_HIP(gfa::scratch_free(rem, st));
-            GFA_HIP(launch_err);
+            GFA_HIP(hipGetLastError());
             return GFA_OK;
         }
     }
@@ -2108,9 +2095,10 @@ int gfa_debug_rs_bm_selftest(gfa_field_t *f, int64_t nseq, uint64_t seed, int64_
     }
     uint8_t *d_seq = nullptr;
     int *d_len = nullptr, *d_out = nullptr;
-    GFA_HIP(gfa::scratch_alloc((void **)&d_seq, seqs.size(), st));
-    GFA_HIP(gfa::scratch_alloc((void **)&d_len, lens.size() * sizeof(int), st));
-    GFA_HIP(gfa::scratch_alloc((void **)&d_out, lens.size() * sizeof(int), st));
+    Scratch ws(st);
+    GFA_HIP(ws.get(&d_seq, seqs.size()));
+    GFA_HIP(ws.get(&d_len, lens.size()));
+    GFA_HIP(ws.get(&d_out, lens.size()));
     GFA_HIP(hipMemcpyAsync(d_seq, seqs.data(), seqs.size(), hipMemcpyHostToDevice, st));
     GFA_HIP(hipMemcpyAsync(d_len, lens.data(), lens.size() * sizeof(int), hipMemcpyHostToDevice, st));
     static bool attr = false;
@@ -2122,7 +2110,6 @@ int gfa_debug_rs_bm_selftest(gfa_field_t *f, int64_t nseq, uint64_t seed, int64_
     std::vector<int> out((size_t)nseq);
     GFA_HIP(hipMemcpyAsync(out.data(), d_out, out.size() * sizeof(int), hipMemcpyDeviceToHost, st));
     GFA_HIP(hipStreamSynchronize(st));
-    (void)gfa::scratch_free(d_seq, st); (void)gfa::scratch_free(d_len, st); (void)gfa::scratch_free(d_out, st);
     i64 bad = 0;
     for (int v : out) bad += v != 0;
     *mismatches = bad;

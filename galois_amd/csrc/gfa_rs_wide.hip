@@ -507,12 +507,11 @@ int polydiv_t(gfa_rs *code, const FieldDev &fd, gfa_rs::Dev *cd, const void *cw,
     const int nwaves = 4;
     const int grid = grid_for_waves(batch, nwaves);
     u32 *scratch = nullptr;
-    GFA_HIP(gfa::scratch_alloc((void **)&scratch, sizeof(u32) * (size_t)grid * nwaves * (size_t)ns, st));
+    Scratch ws(st);
+    GFA_HIP(ws.get(&scratch, (size_t)grid * nwaves * (size_t)ns));
     hipLaunchKernelGGL((wide_polydiv_kernel<TS>), dim3(grid), dim3(nwaves * 64), 0, st, fd, rp, cd->gw, (const TS *)cw, (int)ns, (TS *)out,
                        batch, scratch);
-    const hipError_t e = hipGetLastError();
-    (void)gfa::scratch_free(scratch, st);
-    GFA_HIP(e);
+    GFA_HIP(hipGetLastError());
     return GFA_OK;
 }
 
@@ -572,13 +571,12 @@ int rs_wide_decode(gfa_rs *code, const void *recv, const uint8_t *eras, i64 ns, 
     const FieldDev fd = code->field->lut_desc(*ds);
     if (!detect_only && out == recv) {
         // the kernel reads the received row while it writes the output row: decode in place through a copy of the input
-        void *tmp = nullptr;
+        Scratch ws(st); // outlives the recursive call
+        uint8_t *tmp = nullptr;
         const size_t bytes = dtype_size(dtype) * (size_t)batch * (size_t)ns;
-        GFA_HIP(gfa::scratch_alloc(&tmp, bytes, st));
+        GFA_HIP(ws.get(&tmp, bytes));
         GFA_HIP(hipMemcpyAsync(tmp, recv, bytes, hipMemcpyDeviceToDevice, st));
-        rc = rs_wide_decode(code, tmp, eras, ns, out, nerr, detected, batch, false, dtype, st);
-        (void)gfa::scratch_free(tmp, st);
-        return rc;
+        return rs_wide_decode(code, tmp, eras, ns, out, nerr, detected, batch, false, dtype, st);
     }
     GFA_WIDE_DISPATCH(decode_t, code, fd, cd, recv, eras, ns, out, nerr, detected, batch, detect_only, st);
 }

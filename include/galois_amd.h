@@ -393,6 +393,9 @@ void gfa_debug_m32_tune(int key, int value);
  * _lfsr.py:1647-1702, inside bch_decode_jit) against a compiler-generated loop of the same recurrence, on `nseq` syndrome
  * sequences derived from `seed` over a GF(2^8) field; *mismatches = sequences on which the two disagree (must be 0). */
 int gfa_debug_rs_bm_selftest(gfa_field_t *f, int64_t nseq, uint64_t seed, int64_t *mismatches, gfa_stream_t stream);
+/* Test-only: bytes currently allocated from the current device's work-buffer pool (hipMemPoolAttrUsedMemCurrent); -1 when the
+ * library runs on the device's default pool or the runtime refuses the query. */
+int64_t gfa_debug_scratch_in_use(void);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
