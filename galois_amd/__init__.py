@@ -15,12 +15,14 @@ from ._ntt import ntt, intt  # noqa: E402
 from ._codes import BCH, ReedSolomon  # noqa: E402
 from ._poly import Poly, berlekamp_massey  # noqa: E402
 from ._numtheory import (  # noqa: E402
-    is_prime, factors, primitive_root, is_primitive_root, matlab_primitive_poly, conway_poly, primitive_poly,
+    is_prime, primitive_root, is_primitive_root, matlab_primitive_poly, conway_poly, primitive_poly,
 )
 from ._polysearch import (  # noqa: E402
     irreducible_poly, irreducible_polys, primitive_polys, is_irreducible_batched, is_primitive_batched,
 )
 from ._polydiv import poly_divmod_batched, poly_powmod_batched  # noqa: E402
+from ._polygcd import gcd, egcd, lcm, prod, poly_gcd_batched, poly_egcd_batched, gcd_max_terms  # noqa: E402
+from ._polyfactor import factors  # noqa: E402  (also gives Poly its factorisation methods)
 from . import _dist as dist  # noqa: E402
 from . import _linalg as linalg  # noqa: E402
 
@@ -29,6 +31,7 @@ GF2 = GF(2)
 __all__ = [
     "FieldArray", "GF", "GF2", "Field", "ntt", "intt", "ReedSolomon", "BCH", "Poly", "berlekamp_massey", "is_prime", "factors", "primitive_root",
     "is_primitive_root", "matlab_primitive_poly", "conway_poly", "primitive_poly", "irreducible_poly", "irreducible_polys", "primitive_polys",
-    "is_irreducible_batched", "is_primitive_batched", "poly_divmod_batched", "poly_powmod_batched", "dist", "linalg",
+    "is_irreducible_batched", "is_primitive_batched", "poly_divmod_batched", "poly_powmod_batched", "gcd", "egcd", "lcm", "prod",
+    "poly_gcd_batched", "poly_egcd_batched", "gcd_max_terms", "dist", "linalg",
 ]
 __version__ = "0.1.0"

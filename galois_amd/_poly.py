@@ -9,8 +9,10 @@ array-sized work.  Paths relative to /roo
                                                                  _poly.py:372-530 (the tests run in galois_amd/_polysearch.py)
   * divmod, //, %, ** and three-argument pow() .................. _polys/_poly.py:1327-1460 over divmod_jit / floordiv_jit /
                                                                  mod_jit / pow_jit (_polys/_dense.py:126-401; galois_amd/_polydiv.py)
-Everything built on the remainder (gcd, factoring, roots, interpolation, LFSRs) and the sparse/binary representations stay out of
-scope.
+  * gcd / egcd / lcm / prod, is_square_free() and the factorisations ... _polys/_functions.py:10-94 and _polys/_factor.py:15-450
+                                                                 (galois_amd/_polygcd.py on gfa_poly_gcd; galois_amd/_polyfactor.py,
+                                                                 which also adds Poly.Random and Poly.is_monic)
+Root finding, interpolation, polynomial crt, LFSRs and the sparse/binary representations stay out of scope.
 """
 from __future__ import annotations
 

@@ -320,6 +320,21 @@ int gfa_poly_divmod(gfa_field_t *f, const void *a, int64_t batch, int64_t na, co
  * gfa_convolve and gfa_poly_divmod instead, as galois_amd/_polydiv.py does). */
 int gfa_poly_powmod(gfa_field_t *f, const void *a, int64_t batch, int64_t na, const uint64_t *exp_limbs, int64_t n_limbs, const void *c,
                     int64_t nc, void *out, int dtype, gfa_stream_t stream);
+/* gcd / egcd of polynomials (_polys/_functions.py:10-57) for `batch` pairs: a is batch x na device coefficients, row-major,
+ * highest degree first; b is b_rows x nb with b_rows == batch (pair k is (a_k, b_k)) or b_rows == 1 (one b for every row).
+ * Leading zeros are allowed in every row, so the rows of a stack may have different degrees.  With n = max(na, nb), g_out receives
+ * batch x n coefficients of the MONIC gcd, right-aligned and zero-filled on the left: the last non-zero remainder divided by its
+ * leading coefficient; gcd(0, 0) = 0 and gcd(a, 0) = a / lead(a).  s_out and t_out (both or neither; batch x n, same layout)
+ * receive egcd's cofactors, a_k s_k + b_k t_k = g_k, with the reference's values (s2 <- s2 - q s1 from (1, 0), t from (0, 1),
+ * divided by the same leading coefficient; (s, t) = (1, 0) for gcd(0, 0)).  deg_out (device, batch entries, nullable) receives
+ * deg g_k, -1 for the zero polynomial -- what a caller needs to steer on without reading coefficients back.  The outputs do not
+ * alias the inputs.  One workgroup per pair runs the whole remainder sequence in one launch with the remainders (and cofactors) in
+ * LDS (gfa_polygcd.h), which caps na + nb at 38398 (19199 on 64-bit elements: every field but prime fields below 2^32 and table
+ * fields), and at 12799 (6399) when s_out and t_out are given; above the cap GFA_ERR_UNSUPPORTED with a message that names it
+ * (run Euclid over gfa_poly_divmod instead, as galois_amd/_polygcd.py does).  f == NULL -- fields of order >= 2^64 have no
+ * gfa_field_t -- is GFA_ERR_UNSUPPORTED as well.  At most 2^31 - 1 rows. */
+int gfa_poly_gcd(gfa_field_t *f, const void *a, int64_t batch, int64_t na, const void *b, int64_t b_rows, int64_t nb, void *g_out, void *s_out,
+                 void *t_out, int32_t *deg_out, int dtype, gfa_stream_t stream);
 
 /* ---- Reed-Solomon -------------------------------------------------------------------------------- *
  * gfa_rs_create replaces the arithmetic part of ReedSolomon.__init__ (_codes/_reed_solomon.py:111-218) and
