@@ -89,6 +89,8 @@ SIGNATURES = {
     "gfa_poly_divmod": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_void_p, c_int, c_void_p]),
     "gfa_poly_powmod": (c_int, [c_void_p, c_void_p, c_i64, c_i64, _u64p, c_i64, c_void_p, c_i64, c_void_p, c_int, c_void_p]),
     "gfa_poly_gcd": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "gfa_poly_roots": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "gfa_poly_root_multiplicity": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_int, c_void_p]),
     "gfa_time_matmul": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, c_void_p, c_int,
                                 ctypes.POINTER(ctypes.c_float)]),
     "gfa_rs_create": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_u64, c_int, ctypes.POINTER(c_void_p)]),

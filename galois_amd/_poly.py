@@ -12,7 +12,10 @@ array-sized work.  Paths relative to /roo
   * gcd / egcd / lcm / prod, is_square_free() and the factorisations ... _polys/_functions.py:10-94 and _polys/_factor.py:15-450
                                                                  (galois_amd/_polygcd.py on gfa_poly_gcd; galois_amd/_polyfactor.py,
                                                                  which also adds Poly.Random and Poly.is_monic)
-Root finding, interpolation, polynomial crt, LFSRs and the sparse/binary representations stay out of scope.
+  * roots(multiplicity) and Poly.Roots .......................... _polys/_poly.py:706-787 over roots_jit (_polys/_dense.py:443-513) and
+                                                                 _root_multiplicity, and _poly.py:536-612 (galois_amd/_polyroots.py on
+                                                                 gfa_poly_roots / gfa_poly_root_multiplicity)
+Interpolation, polynomial crt, LFSRs and the sparse/binary representations stay out of scope.
 """
 from __future__ import annotations
 

@@ -335,6 +335,28 @@ int gfa_poly_powmod(gfa_field_t *f, const void *a, int64_t batch, int64_t na, co
  * gfa_field_t -- is GFA_ERR_UNSUPPORTED as well.  At most 2^31 - 1 rows. */
 int gfa_poly_gcd(gfa_field_t *f, const void *a, int64_t batch, int64_t na, const void *b, int64_t b_rows, int64_t nb, void *g_out, void *s_out,
                  void *t_out, int32_t *deg_out, int dtype, gfa_stream_t stream);
+/* Poly.roots (_polys/_poly.py:706-787 over roots_jit, _polys/_dense.py:443-513, and _root_multiplicity) for `batch` polynomials:
+ * coeffs is batch x ncoef device coefficients, row-major, highest degree first, ncoef >= 2; leading zeros are allowed, so the
+ * rows of a stack may have different degrees.  roots_out receives batch x (ncoef - 1) elements: row k holds the distinct roots
+ * of row k in increasing integer value, then zeros.  count_out (device, batch entries) receives how many there are: 0 for a
+ * non-zero constant, -1 for the zero polynomial, of which every element is a root and for which nothing but the zero fill is
+ * written.  mult_out (device, batch x (ncoef - 1) int32, nullable) receives at j the multiplicity of root j -- the largest m
+ * with (x - r)^m dividing the row -- and 0 in the fill.  The outputs do not alias the inputs; the results are the same on every
+ * run.  Two launches: a search that evaluates the row at every one of the q elements (the integers 0 .. q - 1, generated from
+ * the index) and a finishing kernel, one workgroup per row, that sorts the hits and divides by (x - r) while the remainder is
+ * zero (gfa_polyroots.h).  The search is q (ncoef - 1) batch evaluation steps: above 2^42 of them GFA_ERR_UNSUPPORTED (find
+ * such roots from gcd(f, x^q - x), as galois_amd/_polyroots.py does).  The finishing kernel holds a row in LDS, which caps
+ * ncoef at 9600 (4800 on 64-bit elements: every field but prime fields below 2^32 and table fields); above the cap
+ * GFA_ERR_UNSUPPORTED with a message that names it.  f == NULL -- fields of order >= 2^64 have no gfa_field_t -- is
+ * GFA_ERR_UNSUPPORTED as well, and so are more than 2^31 - 1 rows or coefficients. */
+int gfa_poly_roots(gfa_field_t *f, const void *coeffs, int64_t batch, int64_t ncoef, void *roots_out, int32_t *mult_out, int64_t *count_out,
+                   int dtype, gfa_stream_t stream);
+/* The second half of gfa_poly_roots on GIVEN elements: roots is batch x nroots device elements, and mult_out (batch x nroots
+ * int32) receives at j the multiplicity of roots[k][j] as a root of row k of coeffs (batch x ncoef, ncoef >= 1): 0 for an
+ * element that is no root, and 0 for every element of a zero row.  The elements need not be sorted or distinct.  Same cap on
+ * ncoef (with nroots counted as ncoef - 1) and same GFA_ERR_UNSUPPORTED cases as gfa_poly_roots. */
+int gfa_poly_root_multiplicity(gfa_field_t *f, const void *coeffs, int64_t batch, int64_t ncoef, const void *roots, int64_t nroots,
+                               int32_t *mult_out, int dtype, gfa_stream_t stream);
 
 /* ---- Reed-Solomon -------------------------------------------------------------------------------- *
  * gfa_rs_create replaces the arithmetic part of ReedSolomon.__init__ (_codes/_reed_solomon.py:111-218) and
