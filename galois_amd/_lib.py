@@ -91,6 +91,7 @@ SIGNATURES = {
     "gfa_poly_gcd": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "gfa_poly_roots": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "gfa_poly_root_multiplicity": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_int, c_void_p]),
+    "gfa_poly_lagrange": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_void_p, c_void_p, c_int, c_void_p]),
     "gfa_time_matmul": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, c_void_p, c_int,
                                 ctypes.POINTER(ctypes.c_float)]),
     "gfa_rs_create": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_u64, c_int, ctypes.POINTER(c_void_p)]),
@@ -108,6 +109,7 @@ SIGNATURES = {
     "gfa_time_rs_decode": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_int, c_void_p, c_int, _f32p]),
     "gfa_debug_fermat_stamps": (None, [c_void_p]),
     "gfa_debug_m32_tune": (None, [c_int, c_int]),
+    "gfa_debug_lagrange_tune": (None, [c_int]),
     "gfa_debug_rs_bm_selftest": (c_int, [c_void_p, c_i64, c_u64, _i64p, c_void_p]),
     "gfa_debug_scratch_in_use": (c_i64, []),
 }

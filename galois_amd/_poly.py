@@ -15,7 +15,9 @@ array-sized work.  Paths relative to /roo
   * roots(multiplicity) and Poly.Roots .......................... _polys/_poly.py:706-787 over roots_jit (_polys/_dense.py:443-513) and
                                                                  _root_multiplicity, and _poly.py:536-612 (galois_amd/_polyroots.py on
                                                                  gfa_poly_roots / gfa_poly_root_multiplicity)
-Interpolation, polynomial crt, LFSRs and the sparse/binary representations stay out of scope.
+  * lagrange_poly, lagrange_poly_batched and crt ................ _polys/_lagrange.py:19-133 and _polymorphic.py:386-521
+                                                                 (galois_amd/_lagrange.py on gfa_poly_lagrange)
+LFSRs and the sparse/binary representations stay out of scope.
 """
 from __future__ import annotations
 

@@ -357,6 +357,19 @@ int gfa_poly_roots(gfa_field_t *f, const void *coeffs, int64_t batch, int64_t nc
  * ncoef (with nroots counted as ncoef - 1) and same GFA_ERR_UNSUPPORTED cases as gfa_poly_roots. */
 int gfa_poly_root_multiplicity(gfa_field_t *f, const void *coeffs, int64_t batch, int64_t ncoef, const void *roots, int64_t nroots,
                                int32_t *mult_out, int dtype, gfa_stream_t stream);
+/* lagrange_poly (_polys/_lagrange.py:19-74 over lagrange_poly_jit, :77-133) for `batch` point sets: x is x_rows x npts device
+ * elements, row-major, with x_rows == batch, or x_rows == 1 for abscissae shared by every row; y is batch x npts.  coeffs_out
+ * receives batch x npts coefficients of the unique L_k with deg L_k < npts and L_k(x[k][i]) = y[k][i], highest degree first,
+ * leading zeros kept.  status_out (device, batch int32) receives 0, or 1 for a row whose x has a repeated entry: that row of
+ * coeffs_out is then all zero, and every other row is unaffected.  The outputs do not alias the inputs.  One launch without a
+ * work buffer: a team of lanes per row computes the weights prod (x_i - x_m) (a zero weight is the duplicate test), one
+ * inversion per point, and npts sweeps that build L without powers or reductions (gfa_lagrange.h); rows of up to 256 points share
+ * a workgroup.  A row is held in LDS, which caps npts at 6399 (3199 on 64-bit elements: every field but prime fields below 2^32
+ * and table fields); above the cap GFA_ERR_UNSUPPORTED with a message that names it (galois_amd/_lagrange.py then runs the same
+ * sweeps on whole arrays).  f == NULL -- fields of order >= 2^64 have no gfa_field_t -- is GFA_ERR_UNSUPPORTED as well, and so
+ * are more than 2^31 - 1 rows.  batch == 0 is GFA_OK. */
+int gfa_poly_lagrange(gfa_field_t *f, const void *x, const void *y, int64_t batch, int64_t npts, int64_t x_rows, void *coeffs_out,
+                      int32_t *status_out, int dtype, gfa_stream_t stream);
 
 /* ---- Reed-Solomon -------------------------------------------------------------------------------- *
  * gfa_rs_create replaces the arithmetic part of ReedSolomon.__init__ (_codes/_reed_solomon.py:111-218) and
@@ -426,6 +439,9 @@ void gfa_debug_fermat_stamps(unsigned long long *buf);
 /* tuning aid of the signed-Montgomery NTT kernels (tools/m32_tune3.py): key 0 / 1 = line lengths (log2) of the first / second pass of the
  * three-pass form (0: default), 2 = non-temporal last pass (-1 by size, 0 never, 1 always), 3 = 1024-thread workgroups in the last pass */
 void gfa_debug_m32_tune(int key, int value);
+/* tuning aid of gfa_poly_lagrange (tools/bench_lagrange.py): the threads of a workgroup that rows share, and the largest npts
+ * that is packed -- a power of two in [64, 1024]; anything else restores the default */
+void gfa_debug_lagrange_tune(int pack_threads);
 /* Test-only: the hand-assembled Berlekamp-Massey loop of the Reed-Solomon wave decoder (replaces berlekamp_massey_jit,
  * _lfsr.py:1647-1702, inside bch_decode_jit) against a compiler-generated loop of the same recurrence, on `nseq` syndrome
  * sequences derived from `seed` over a GF(2^8) field; *mismatches = sequences on which the two disagree (must be 0). */
