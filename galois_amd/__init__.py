@@ -25,6 +25,7 @@ from ._polygcd import gcd, egcd, lcm, prod, poly_gcd_batched, poly_egcd_batched,
 from ._polyfactor import factors  # noqa: E402  (also gives Poly its factorisation methods)
 from ._polyroots import poly_roots_batched, roots_max_terms  # noqa: E402  (also gives Poly its roots() and Roots())
 from ._lagrange import lagrange_poly, lagrange_poly_batched, lagrange_max_points, crt  # noqa: E402
+from ._lfsr import FLFSR, GLFSR, lfsr_step_batched, lfsr_max_order  # noqa: E402
 from . import _dist as dist  # noqa: E402
 from . import _linalg as linalg  # noqa: E402
 
@@ -35,6 +36,6 @@ __all__ = [
     "is_primitive_root", "matlab_primitive_poly", "conway_poly", "primitive_poly", "irreducible_poly", "irreducible_polys", "primitive_polys",
     "is_irreducible_batched", "is_primitive_batched", "poly_divmod_batched", "poly_powmod_batched", "gcd", "egcd", "lcm", "prod",
     "poly_gcd_batched", "poly_egcd_batched", "gcd_max_terms", "poly_roots_batched", "roots_max_terms", "lagrange_poly",
-    "lagrange_poly_batched", "lagrange_max_points", "crt", "dist", "linalg",
+    "lagrange_poly_batched", "lagrange_max_points", "crt", "FLFSR", "GLFSR", "lfsr_step_batched", "lfsr_max_order", "dist", "linalg",
 ]
 __version__ = "0.1.0"

@@ -92,7 +92,10 @@ SIGNATURES = {
     "gfa_poly_roots": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "gfa_poly_root_multiplicity": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_int, c_void_p]),
     "gfa_poly_lagrange": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_void_p, c_void_p, c_int, c_void_p]),
-    "gfa_time_matmul": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, c_void_p, c_int,
+    "gfa_lfsr_step": (c_int, [c_void_p, c_int, c_int, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_int, c_void_p]),
+    "gfa_lfsr_jump": (c_int, [c_void_p, c_int, c_void_p, c_i64, c_void_p, _u64p, c_i64, c_u64, c_i64, c_void_p, c_int, c_void_p]),
+    "gfa_lfsr_max_order": (c_i64, [c_void_p]),
+    "gfa_time_matmul":(c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, c_void_p, c_int,
                                 ctypes.POINTER(ctypes.c_float)]),
     "gfa_rs_create": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_u64, c_int, ctypes.POINTER(c_void_p)]),
     "gfa_bch_create": (c_int, [c_void_p, c_u64, c_i64, c_i64, c_i64, c_i64, c_u64, _u64p, c_int, ctypes.POINTER(c_void_p)]),

@@ -17,7 +17,8 @@ array-sized work.  Paths relative to /roo
                                                                  gfa_poly_roots / gfa_poly_root_multiplicity)
   * lagrange_poly, lagrange_poly_batched and crt ................ _polys/_lagrange.py:19-133 and _polymorphic.py:386-521
                                                                  (galois_amd/_lagrange.py on gfa_poly_lagrange)
-LFSRs and the sparse/binary representations stay out of scope.
+  * reverse(), Identity, coefficients(size, order) ............... _polys/_poly.py:229-256, 618-703 (what galois_amd/_lfsr.py needs)
+The sparse/binary representations stay out of scope.
 """
 from __future__ import annotations
 
@@ -99,6 +100,37 @@ class Poly:
         for d, c in zip(degrees, coeffs):
             dense[len(dense) - 1 - d] = c
         return cls(field(np.array(dense, dtype=object)))
+
+    @classmethod
+    def Identity(cls, field=None) -> "Poly":
+        """Poly.Identity (_polys/_poly.py:229-256): the polynomial x."""
+        if field is None:
+            from ._factory import GF
+
+            field = GF(2)
+        return cls(field([1, 0]))
+
+    def coefficients(self, size=None, order: str = "desc") -> FieldArray:
+        """Poly.coefficients (_polys/_poly.py:618-678): the coefficients in `size` >= degree + 1 entries, zeros for the higher
+        degrees, highest degree first or ("asc") last."""
+        if not (size is None or isinstance(size, (int, np.integer))):
+            raise TypeError(f"Argument 'size' must be an instance of {int}, not {type(size)}.")
+        if not isinstance(order, str):
+            raise TypeError(f"Argument 'order' must be an instance of {str}, not {type(order)}.")
+        n = self._coeffs.size
+        size = n if size is None else int(size)
+        if not size >= n:
+            raise ValueError(f"Argument 'size' must be at least degree + 1 ({n}), not {size}.")
+        if order not in ["desc", "asc"]:
+            raise ValueError(f"Argument 'order' must be either 'desc' or 'asc', not {order!r}.")
+        F = self._field
+        zeros = F.Zeros(size - n) if F._limbed else F.Zeros(size - n, dtype=self._coeffs.dtype)
+        coeffs = self._coeffs.copy() if size == n else np.concatenate([zeros, self._coeffs])
+        return np.flip(coeffs, axis=0) if order == "asc" else coeffs
+
+    def reverse(self) -> "Poly":
+        """Poly.reverse (_polys/_poly.py:680-703): x^d f(1/x) for the degree d -- the coefficients reversed."""
+        return Poly(np.flip(self._coeffs, axis=0))
 
     def __int__(self) -> int:
         """The integer whose radix-q digits are the coefficients (_polys/_poly.py:752-775)."""
@@ -261,10 +293,10 @@ class Poly:
         return p
 
 
-def berlekamp_massey(sequence, output: str = "minimal") -> Poly:
+def berlekamp_massey(sequence, output: str = "minimal"):
     """galois.berlekamp_massey (_lfsr.py:1560-1625): the minimal (characteristic) polynomial c(x) of a linear recurrent
-    sequence, or its connection polynomial C(x) = reverse of c(x).  The LFSR-object outputs of the reference ("fibonacci",
-    "galois") are out of scope."""
+    sequence, or its connection polynomial C(x) = reverse of c(x); "fibonacci" and "galois" give the register that puts the
+    sequence out next (_lfsr.py:1613-1619): its state is the first deg C values reversed."""
     if not isinstance(sequence, FieldArray):
         raise TypeError(f"Argument 'sequence' must be a FieldArray, not {type(sequence)}.")
     if not isinstance(output, str):
@@ -273,8 +305,6 @@ def berlekamp_massey(sequence, output: str = "minimal") -> Poly:
         raise ValueError(f"Argument 'sequence' must be 1-D, not {sequence.ndim}-D.")
     if output not in ["minimal", "connection", "fibonacci", "galois"]:
         raise ValueError(f"Argument 'output' must be in ['minimal', 'connection', 'fibonacci', 'galois'], not {output!r}.")
-    if output in ["fibonacci", "galois"]:
-        raise NotImplementedError("LFSR objects are outside this engine; use output='minimal' or 'connection'.")
     F = type(sequence)
     t = sequence._t.contiguous()
     n = t.numel()
@@ -283,6 +313,12 @@ def berlekamp_massey(sequence, output: str = "minimal") -> Poly:
     L.check(L.lib().gfa_berlekamp_massey(F._handle, _ptr(t), n, 1, _ptr(out), _ptr(ln), sequence._gfa_dtype(), _stream()),
             "gfa_berlekamp_massey")
     asc = out[: int(ln.item())]
-    if output == "connection":
-        return Poly(F._wrap(torch.flip(asc, dims=(0,)).contiguous(), sequence._np_dtype))  # degree-descending C(x)
+    if output != "minimal":
+        connection = Poly(F._wrap(torch.flip(asc, dims=(0,)).contiguous(), sequence._np_dtype))  # degree-descending C(x)
+        if output == "connection":
+            return connection
+        from ._lfsr import FLFSR
+
+        lfsr = FLFSR(connection, state=np.flip(sequence[0:connection.degree], axis=0))
+        return lfsr if output == "fibonacci" else lfsr.to_galois_lfsr()
     return Poly(F._wrap(asc.contiguous(), sequence._np_dtype))  # c(x) = x^L C(1/x): the ascending C read as descending

@@ -370,6 +370,31 @@ int gfa_poly_root_multiplicity(gfa_field_t *f, const void *coeffs, int64_t batch
  * are more than 2^31 - 1 rows.  batch == 0 is GFA_OK. */
 int gfa_poly_lagrange(gfa_field_t *f, const void *x, const void *y, int64_t batch, int64_t npts, int64_t x_rows, void *coeffs_out,
                       int32_t *status_out, int dtype, gfa_stream_t stream);
+/* The four step loops of FLFSR / GLFSR (_lfsr.py:763-777, 826-843, 1398-1415, 1463-1477) for `batch` registers of order n with the
+ * same taps, one launch: kind 0 is a Fibonacci register (taps -a_1 .. -a_n), kind 1 a Galois register (taps -a_n .. -a_1);
+ * direction 1 steps forward, -1 backward (the tap a_n must then be non-zero: a caller error the entry point cannot see, after
+ * which the values are unspecified).  taps is n device elements, states is batch x n device elements, row-major, S[0] first,
+ * and is UPDATED IN PLACE to the states after `steps` clocks; y_out (batch x steps, nullable) receives the outputs in the order
+ * they are produced.  Values are the reference's, bit for bit.  One lane per register with the states in LDS, which caps n at
+ * 19167 (9567 on 64-bit elements: every field but prime fields below 2^32 and table fields); over GF(2) forward steps of
+ * registers of at most 64 bits run on one 64-bit word per lane.  Above the cap GFA_ERR_UNSUPPORTED with a message that names it;
+ * f == NULL -- fields of order >= 2^64 have no gfa_field_t -- and more than 2^31 - 1 registers are GFA_ERR_UNSUPPORTED too.
+ * batch == 0 and steps == 0 are GFA_OK. */
+int gfa_lfsr_step(gfa_field_t *f, int kind, int direction, const void *taps, int64_t n, void *states, int64_t batch, int64_t steps,
+                  void *y_out, int dtype, gfa_stream_t stream);
+/* Jump-ahead: row k < count of states_out (count x n) receives the state of ONE register exp0 + k stride forward clocks after
+ * `state` (n device elements), without producing the outputs in between.  P is the n + 1 device coefficients of the
+ * characteristic polynomial x^n + a_1 x^(n-1) + .. + a_n, highest degree first; exp0 >= 0 is n_limbs >= 1 little-endian 64-bit
+ * words in HOST memory (at most 126 significant words; GFA_ERR_UNSUPPORTED beyond).  A Galois state is the polynomial
+ * S[0] + S[1] x + .., one clock multiplies it by x modulo P, so row k is x^(exp0 + k stride) times the state modulo P: one
+ * workgroup per row runs square-and-multiply with the operands in LDS (a set bit costs one clock, not a product).  A Fibonacci
+ * state is converted to the equivalent Galois state and back inside (FLFSR.to_galois_lfsr, _lfsr.py:552-575).  LDS caps n at
+ * gfa_lfsr_max_order(f): 7628, or 3814 on 64-bit elements; above it GFA_ERR_UNSUPPORTED with a message that names the cap (step
+ * instead).  f == NULL is GFA_ERR_UNSUPPORTED, count == 0 is GFA_OK. */
+int gfa_lfsr_jump(gfa_field_t *f, int kind, const void *P, int64_t n, const void *state, const uint64_t *exp0_limbs, int64_t n_limbs,
+                  uint64_t stride, int64_t count, void *states_out, int dtype, gfa_stream_t stream);
+/* the largest order gfa_lfsr_jump serves over the field (0 for f == NULL) */
+int64_t gfa_lfsr_max_order(gfa_field_t *f);
 
 /* ---- Reed-Solomon -------------------------------------------------------------------------------- *
  * gfa_rs_create replaces the arithmetic part of ReedSolomon.__init__ (_codes/_reed_solomon.py:111-218) and
