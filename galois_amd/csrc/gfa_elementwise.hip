@@ -413,6 +413,21 @@ __device__ __forceinline__ u32 lookup4(const uint8_t *lds, u32 aw, u32 bw)
 // order was not what separated this kernel from the flat launch, the output lines allocated in the caches were.  The launch
 // chooses NT_STORE by array size, see launch_tab8_binary.  The flat launch is bimodal (passes at 43.6 .. 43.9 and at 46.8 .. 48.8);
 // against its MEDIAN this kernel had no gap left to close, against its best pass the non-temporal stores close 92 % of it.
+// r08, the prologue: the table goes to LDS through stage_table_lds (gfa_internal.h) -- behind the two operand loads a lane issues
+// its four table loads together and writes LDS behind vmcnt(3) .. vmcnt(0), six requests in flight and ONE round trip to L2
+// before the barrier.  The `dst[t] = src[t]` loop it replaces was not unrolled: four dependent round trips per workgroup, every
+// workgroup of the launch in that phase at the same moment and no HBM request in flight after the first.
+// tools/ubench/stream5.hip, variants interleaved, medians of 7 x 100 launches in two passes (profiles/r08_tab8_staging.txt), us:
+//                                      1e8 (nt stores)   2^26 (nt)   2^27 (nt)   2^24 (ordinary stores)
+//   r07 prologue                        43.70 / 43.87      30.14       59.20        9.59
+//   batched staging (this kernel)       42.95 / 43.10      29.08       58.32        8.43
+//   + one workgroup per CU, 2 vectors   43.94 / 44.09      30.13       59.95        9.67     rejected
+//   + loads two rounds ahead            43.41 / 43.61      29.41       59.32        9.98     rejected
+//   a ^ b, same shape (no table)        42.46 / 42.63      28.79       56.97        7.47
+//   copy of 1.5 n bytes, same shape     43.87 / 43.87      29.61       58.27        7.59
+// (max - min of a row's seven passes: 0.06 .. 0.23 us).  What is left above the table-free stream is 0.5 us at 1e8.
+// bench.py with its defaults, six runs per library alternating with the parent: median 43.86 -> 42.98 us per step (max - min
+// 0.16 / 0.35 us); rocprofv3 kernel average over 500 launches 44.01 -> 43.18 us; the products equal element for element.
 template <bool CHECK_ZERO_B, bool NT_STORE>
 __global__ __launch_bounds__(TAB8_THREADS) void tab8_binary_kernel(const uint8_t *__restrict__ table,
                                                                     const uint8_t *__restrict__ a,
@@ -428,11 +443,7 @@ __global__ __launch_bounds__(TAB8_THREADS) void tab8_binary_kernel(const uint8_t
     i64 i = (i64)blockIdx.x * TAB8_THREADS + threadIdx.x;
     u32x4 x = {0, 0, 0, 0}, y = {0, 0, 0, 0};
     if (i < nvec) { x = av[i]; y = bv[i]; }
-    {
-        const uint4 *src = reinterpret_cast<const uint4 *>(table);
-        uint4 *dst = reinterpret_cast<uint4 *>(lds);
-        for (int t = threadIdx.x; t < 65536 / 16; t += TAB8_THREADS) dst[t] = src[t];
-    }
+    stage_table_lds<TAB8_THREADS>(lds, table, 65536 / 16);
     __syncthreads();
     bool bad = false;
     for (; i < nvec; i += stride) {
@@ -484,7 +495,11 @@ __global__ __launch_bounds__(TAB8_THREADS) void tab8_binary_claim_kernel(const u
     const u32x4 *bv = reinterpret_cast<const u32x4 *>(b);
     u32x4 *ov = reinterpret_cast<u32x4 *>(out);
     i64 blk = blockIdx.x; // the first block of every workgroup is static
+    // A vector past the end of the array is not loaded but still looked up and zero-checked (never stored): its registers keep
+    // what they held, so they start without a zero byte -- a zero left there by an earlier block has been flagged already.
     u32x4 x[U], y[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) { x[u] = u32x4{0, 0, 0, 0}; y[u] = u32x4{~0u, ~0u, ~0u, ~0u}; }
     auto issue = [&](i64 bk) {
 #pragma unroll
         for (int u = 0; u < U; u++) {
@@ -493,11 +508,7 @@ __global__ __launch_bounds__(TAB8_THREADS) void tab8_binary_claim_kernel(const u
         }
     };
     if (blk < nblk) issue(blk);
-    {
-        const uint4 *src = reinterpret_cast<const uint4 *>(table);
-        uint4 *dst = reinterpret_cast<uint4 *>(lds);
-        for (int t = threadIdx.x; t < 65536 / 16; t += TAB8_THREADS) dst[t] = src[t];
-    }
+    stage_table_lds<TAB8_THREADS>(lds, table, 65536 / 16);
     __syncthreads();
     bool bad = false;
     while (blk < nblk) {
@@ -1038,6 +1049,12 @@ static int launch_tab8_claim(int grid, const uint8_t *table, const void *a, cons
 //   static, ordinary stores       46.6     150.7    587.4
 //   static, non-temporal stores   44.1     145.7    572.9
 //   claimed 32 KiB blocks         58.3     138.4    485.4
+// r08 (tools/ubench/stream5.hip, profiles/r08_tab8_staging.txt), the static kernel before / after its table staging was batched:
+//                                  2^24     2^26     1e8      2^27
+//   static, ordinary stores     9.59 / 8.43
+//   static, non-temporal stores          30.14 / 29.08   43.70 / 42.95   59.20 / 58.32
+// One workgroup per CU with two vector pairs per lane, and loads two rounds ahead, both lost to it at all four sizes, so the
+// grid and the schedule are those of r07.
 // so the claim kernel keeps its 2^28 lower bound (it loses below and wins from there), and the static kernel stores
 // non-temporally in the range where that was measured to win.  Its lower end, 2^26 elements, is NOT a measured crossover: it is
 // the size from which operands and result (3 x 64 MiB) no longer leave room in the 256 MiB Infinity Cache for a consumer to find

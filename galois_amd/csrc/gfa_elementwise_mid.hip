@@ -126,12 +126,7 @@ __global__ __launch_bounds__(THREADS) void mid_kernel(MidDesc d, const typename 
         if (sa) x = av[i];
         if (BINARY && sb) y = bv[i];
     }
-    {
-        const int words = (int)((d.qa + d.exp_len + (NEED_ZECH ? d.qa : 0u)) / 8u); // 16-byte units
-        const uint4 *src = reinterpret_cast<const uint4 *>(d.image);
-        uint4 *dst = reinterpret_cast<uint4 *>(mid_lds);
-        for (int t = threadIdx.x; t < words; t += THREADS) dst[t] = src[t];
-    }
+    stage_table_lds<THREADS>(mid_lds, d.image, (int)((d.qa + d.exp_len + (NEED_ZECH ? d.qa : 0u)) / 8u)); // 16-byte units
     __syncthreads();
     MidTabs t;
     t.lg = mid_lds;
@@ -208,12 +203,7 @@ __global__ __launch_bounds__(THREADS) void mid_powv_kernel(MidDesc d, const u16 
     u32x4 *ov = reinterpret_cast<u32x4 *>(out);
     const i64 stride = (i64)gridDim.x * THREADS;
     i64 i = (i64)blockIdx.x * THREADS + threadIdx.x;
-    {
-        const int words = (int)((d.qa + d.exp_len) / 8u); // the index is below q - 1 whatever the length of EXP
-        const uint4 *src = reinterpret_cast<const uint4 *>(d.image);
-        uint4 *dst = reinterpret_cast<uint4 *>(mid_lds);
-        for (int t = threadIdx.x; t < words; t += THREADS) dst[t] = src[t];
-    }
+    stage_table_lds<THREADS>(mid_lds, d.image, (int)((d.qa + d.exp_len) / 8u)); // the index is below q - 1 whatever the length of EXP
     __syncthreads();
     const u16 *lg = mid_lds, *ex = mid_lds + d.qa;
     bool bad = false;

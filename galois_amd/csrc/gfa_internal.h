@@ -69,6 +69,33 @@ __device__ __forceinline__ void flag_error(int32_t *err, bool bad)
     }
 }
 
+// Table image, global memory -> LDS: `units` 16-byte units copied by the THREADS lanes of a workgroup, unit t by lane t % THREADS.
+// A lane issues the four loads of a batch back to back and only then writes LDS, so a batch is ONE round trip to L2 with
+// counted waits (vmcnt(3) .. vmcnt(0)) in front of the writes; the plain `dst[t] = src[t]` loop is not unrolled by the compiler
+// and pays one dependent round trip per unit and lane (profiles/r08_tab8_staging.txt).  The batch has NO branch in it: a unit
+// index past the end of the image is clamped to the last unit, for the load and for the write alike, so such a lane copies the
+// last unit once more (the same bytes to the same place as the lane that owns it).  A guard around the write instead makes the
+// compiler sink each load into the guarded block, next to its write, and the batch is four round trips again.  With `units` a
+// compile-time multiple of 4 * THREADS the clamps fold away.  The caller puts the barrier behind it.
+template <int THREADS>
+__device__ __forceinline__ void stage_table_lds(void *lds, const void *image, int units)
+{
+    constexpr int BATCH = 4;
+    const uint4 *src = reinterpret_cast<const uint4 *>(image);
+    uint4 *dst = reinterpret_cast<uint4 *>(lds);
+    for (int base = threadIdx.x; base < units; base += BATCH * THREADS) {
+        int t[BATCH];
+        uint4 v[BATCH];
+#pragma unroll
+        for (int k = 0; k < BATCH; k++) {
+            t[k] = min(base + k * THREADS, units - 1);
+            v[k] = src[t[k]];
+        }
+#pragma unroll
+        for (int k = 0; k < BATCH; k++) dst[t[k]] = v[k];
+    }
+}
+
 template <class F, int OP>
 __device__ __forceinline__ typename F::elem apply_binary(const FieldDev &fd, typename F::elem x, typename F::elem y, bool &bad)
 {
