@@ -700,14 +700,20 @@ class FieldArray(metaclass=FieldArrayMeta):
             axis = axis % t.dim()
             t2 = t.movedim(axis, -1).contiguous()
             out_shape = tuple(t2.shape[:-1])
-            t2 = t2.reshape(-1, t2.shape[-1])
+            t2 = t2.reshape(int(np.prod(out_shape, dtype=np.int64)), t2.shape[-1])  # (an explicit row count: the axis may be empty)
         t2 = t2.contiguous()
         out = torch.empty(t2.shape[0], dtype=t.dtype, device=t.device)
-        err = torch.zeros(1, dtype=torch.int32, device=t.device) if op == L.OP_DIV else None
-        L.check(L.lib().gfa_reduce(cls._handle, op, _ptr(t2), _ptr(out), t2.shape[0], t2.shape[1], self._gfa_dtype(),
-                                   _stream(), _ptr(err) if err is not None else None), "gfa_reduce")
-        if err is not None:
-            self._check_err(err)
+        if t2.shape[1] == 0:
+            # an empty axis folds to the identity of add / multiply; subtract / divide have none (NumPy's rule)
+            if op not in (L.OP_ADD, L.OP_MUL):
+                raise ValueError("zero-size array to reduction operation which has no identity")
+            out.fill_(1 if op == L.OP_MUL else 0)
+        else:
+            err = torch.zeros(1, dtype=torch.int32, device=t.device) if op == L.OP_DIV else None
+            L.check(L.lib().gfa_reduce(cls._handle, op, _ptr(t2), _ptr(out), t2.shape[0], t2.shape[1], self._gfa_dtype(),
+                                       _stream(), _ptr(err) if err is not None else None), "gfa_reduce")
+            if err is not None:
+                self._check_err(err)
         out = out.reshape(out_shape)
         if keepdims:
             out = out.unsqueeze(axis if axis is not None else 0) if axis is not None else out.reshape((1,) * t.dim())
@@ -791,7 +797,7 @@ class FieldArray(metaclass=FieldArrayMeta):
         axis = axis % t.dim()
         t2 = t.movedim(axis, -1).contiguous()
         shape = t2.shape
-        t2 = t2.reshape(-1, shape[-1])
+        t2 = t2.reshape(int(np.prod(shape[:-1], dtype=np.int64)), shape[-1])  # (an explicit row count: the axis may be empty)
         out = torch.empty_like(t2)
         err = torch.zeros(1, dtype=torch.int32, device=t.device) if op == L.OP_DIV else None
         L.check(L.lib().gfa_accumulate(cls._handle, op, _ptr(t2), _ptr(out), t2.shape[0], t2.shape[1], self._gfa_dtype(),

@@ -4,6 +4,7 @@
 #include <map>
 
 #include "gfa_internal.h"
+#include "gfa_reduce_plan.h"
 
 using namespace gfa;
 
@@ -312,11 +313,8 @@ void reduce_phase1(const FieldDev &fd, const ByteTables &bt, bool is_mul, const 
                    hipStream_t st)
 {
     const unsigned grid = (unsigned)(n_outer * nseg);
-    int stream_mode = -1;
-    if (!is_mul && fd.p == 2) stream_mode = 0;
-    else if (!is_mul && fd.m == 1 && sizeof(T) <= 4 && seg_len < ((i64)1 << 32)) stream_mode = 1;
-    else if (is_mul && std::is_same<F, Lut>::value && sizeof(T) == 1 && fd.q <= 256 && bt.log8 && bt.exp8 && seg_len < ((i64)1 << 40)) stream_mode = 2;
-    else if (!is_mul && std::is_same<F, Lut>::value && sizeof(T) == 1 && fd.q <= 256 && fd.m > 1 && bt.add8) stream_mode = 3; // odd-characteristic table fields: the sum table in LDS
+    // (gfa_reduce_plan.h; 3: odd-characteristic table fields, the sum table in LDS)
+    const int stream_mode = reduce_plan::stream_mode(is_mul, fd.p, fd.m, fd.q, std::is_same<F, Lut>::value, (int)sizeof(T), bt.log8 && bt.exp8, bt.add8 != nullptr, seg_len);
     if (stream_mode == 0)
         hipLaunchKernelGGL((reduce_stream_kernel<T, 0>), dim3(grid), dim3(256), 0, st, (const T *)a, n_inner, col_begin, seg_len, nseg, partial, (u64)fd.p, nullptr, nullptr, 0u);
     else if (stream_mode == 1)
@@ -343,20 +341,14 @@ int launch_reduce_ft(const FieldDev &fd, const ByteTables &bt, int op, const voi
     const int mode = op == GFA_OP_SUB ? 1 : op == GFA_OP_DIV ? 2 : 0;
     const i64 col_begin = mode ? 1 : 0;
     const i64 len = n_inner - col_begin;
-    // enough segments to fill the chip when there are few rows, at least 4096 elements each
-    i64 nseg = 1;
+    // enough segments to fill the chip when there are few rows, at least 4096 elements each (gfa_reduce_plan.h)
     // (the sum-table fold of reduce_phase1 stages 64 KiB per workgroup: two workgroups per CU, long segments)
-    const bool tab_add = !is_mul && std::is_same<F, Lut>::value && sizeof(T) == 1 && fd.q <= 256 && fd.m > 1 && bt.add8;
-    const i64 want_blocks = (i64)num_cus() * (tab_add ? 2 : 8);
-    if (n_outer < want_blocks && len > 8192) {
-        nseg = std::min<i64>((want_blocks + n_outer - 1) / n_outer, (len + 4095) / 4096);
-        if (nseg > 4096) nseg = 4096;
-    }
-    if (nseg < 1) nseg = 1;
-    const i64 seg_len = len > 0 ? (len + nseg - 1) / nseg : 1;
+    const bool tab_add = reduce_plan::table_sum(is_mul, std::is_same<F, Lut>::value, (int)sizeof(T), fd.q, fd.m, bt.add8 != nullptr);
+    const reduce_plan::Segments sg = reduce_plan::reduce_segments(n_outer, len, num_cus(), tab_add);
+    const i64 nseg = sg.nseg, seg_len = sg.seg_len;
     return with_partials(st, (size_t)(n_outer * nseg), [&](u64 *partial) {
         reduce_phase1<F, T>(fd, bt, is_mul, a, n_inner, col_begin, seg_len, nseg, n_outer, partial, st);
-        if (nseg > 8) { // few rows, many segments: a workgroup per row
+        if (reduce_plan::block_join(nseg)) { // few rows, many segments: a workgroup per row
             if (is_mul)
                 hipLaunchKernelGGL((reduce_finalize_block_kernel<F, T, true>), dim3((unsigned)n_outer), dim3(256), 0, st, fd, (const T *)a, n_inner, partial, nseg, (T *)out, mode, err);
             else
@@ -455,7 +447,7 @@ __global__ __launch_bounds__(256) void accumulate_carries_kernel(FieldDev fd, u6
     __shared__ u64 sh[256];
     const i64 row = blockIdx.x;
     const E ident = IS_MUL ? F::one(fd) : (E)0;
-    const i64 c = (nseg + 255) / 256, lo = (i64)threadIdx.x * c;
+    const i64 c = reduce_plan::carry_runs(nseg), lo = (i64)threadIdx.x * c;
     i64 hi = lo + c;
     if (hi > nseg) hi = nseg;
     u64 *pr = partial + row * nseg;
@@ -488,26 +480,21 @@ int launch_accumulate_ft(const FieldDev &fd, const ByteTables &bt, int op, const
     const bool is_mul = op == GFA_OP_MUL || op == GFA_OP_DIV;
     // r06: few long rows (np.cumsum of a 1-D array): segment folds -> carries -> segment scans, instead of one workgroup for the whole row
     const i64 col_begin = mode ? 1 : 0, len = n_inner - col_begin;
-    const i64 want_blocks = (i64)num_cus() * 8;
-    if (n_outer < want_blocks / 4 && len >= ((i64)1 << 16)) {
-        i64 nseg = std::min<i64>((want_blocks + n_outer - 1) / n_outer, len / 8192);
-        if (nseg > 4096) nseg = 4096;
-        if (nseg >= 2) {
-            const i64 seg_len = ((len + nseg - 1) / nseg + 255) / 256 * 256;
-            nseg = (len + seg_len - 1) / seg_len;
-            return with_partials(st, (size_t)(n_outer * nseg), [&](u64 *partial) {
-                reduce_phase1<F, T>(fd, bt, is_mul, a, n_inner, col_begin, seg_len, nseg, n_outer, partial, st);
-                if (is_mul) {
-                    hipLaunchKernelGGL((accumulate_carries_kernel<F, true>), dim3((unsigned)n_outer), dim3(256), 0, st, fd, partial, nseg, n_outer);
-                    hipLaunchKernelGGL((accumulate_kernel<F, T, true>), dim3((unsigned)(n_outer * nseg)), dim3(256), 0, st, fd, (const T *)a, (T *)out, n_inner, mode, err,
-                                       nseg, seg_len, (const u64 *)partial);
-                } else {
-                    hipLaunchKernelGGL((accumulate_carries_kernel<F, false>), dim3((unsigned)n_outer), dim3(256), 0, st, fd, partial, nseg, n_outer);
-                    hipLaunchKernelGGL((accumulate_kernel<F, T, false>), dim3((unsigned)(n_outer * nseg)), dim3(256), 0, st, fd, (const T *)a, (T *)out, n_inner, mode, err,
-                                       nseg, seg_len, (const u64 *)partial);
-                }
-            });
-        }
+    const reduce_plan::Segments sg = reduce_plan::accumulate_segments(n_outer, len, num_cus()); // gfa_reduce_plan.h
+    if (sg.nseg >= 2) {
+        const i64 nseg = sg.nseg, seg_len = sg.seg_len;
+        return with_partials(st, (size_t)(n_outer * nseg), [&](u64 *partial) {
+            reduce_phase1<F, T>(fd, bt, is_mul, a, n_inner, col_begin, seg_len, nseg, n_outer, partial, st);
+            if (is_mul) {
+                hipLaunchKernelGGL((accumulate_carries_kernel<F, true>), dim3((unsigned)n_outer), dim3(256), 0, st, fd, partial, nseg, n_outer);
+                hipLaunchKernelGGL((accumulate_kernel<F, T, true>), dim3((unsigned)(n_outer * nseg)), dim3(256), 0, st, fd, (const T *)a, (T *)out, n_inner, mode, err,
+                                   nseg, seg_len, (const u64 *)partial);
+            } else {
+                hipLaunchKernelGGL((accumulate_carries_kernel<F, false>), dim3((unsigned)n_outer), dim3(256), 0, st, fd, partial, nseg, n_outer);
+                hipLaunchKernelGGL((accumulate_kernel<F, T, false>), dim3((unsigned)(n_outer * nseg)), dim3(256), 0, st, fd, (const T *)a, (T *)out, n_inner, mode, err,
+                                   nseg, seg_len, (const u64 *)partial);
+            }
+        });
     }
     if (is_mul)
         hipLaunchKernelGGL((accumulate_kernel<F, T, true>), dim3((unsigned)n_outer), dim3(256), 0, st, fd, (const T *)a, (T *)out,
@@ -532,12 +519,14 @@ extern "C" {
 int gfa_reduce(gfa_field_t *f, int op, const void *a, void *out, int64_t n_outer, int64_t n_inner, int dtype,
                gfa_stream_t stream, int32_t *dev_err)
 {
-    if (!f || !a || !out || n_outer < 0 || n_inner < 1 || op < GFA_OP_ADD || op > GFA_OP_DIV) {
+    if (!f || n_outer < 0 || n_inner < 1 || op < GFA_OP_ADD || op > GFA_OP_DIV) {
         set_error("gfa_reduce: bad arguments");
         return GFA_ERR_INVALID;
     }
     if (!dtype_holds(dtype, f->calc.q)) { set_error("dtype cannot hold the field's elements"); return GFA_ERR_INVALID; }
-    if (n_outer == 0) return GFA_OK;
+    if (n_outer == 0) return GFA_OK; // (no rows: nothing is read or written, the buffers may be null)
+    if (!a || !out) { set_error("gfa_reduce: bad arguments"); return GFA_ERR_INVALID; }
+    if (!reduce_plan::rows_fit_grid(n_outer)) { set_error("gfa_reduce: more than 2^31 - 1 rows"); return GFA_ERR_INVALID; } // the launch grids
     FieldDeviceState *ds;
     int rc = f->ensure_device(nullptr, &ds);
     if (rc) return rc;
@@ -571,6 +560,7 @@ int gfa_accumulate(gfa_field_t *f, int op, const void *a, void *out, int64_t n_o
     }
     if (n_outer == 0 || n_inner == 0) return GFA_OK;
     if (!a || !out) { set_error("gfa_accumulate: bad arguments"); return GFA_ERR_INVALID; }
+    if (!reduce_plan::rows_fit_grid(n_outer)) { set_error("gfa_accumulate: more than 2^31 - 1 rows"); return GFA_ERR_INVALID; } // the launch grids
     if (!dtype_holds(dtype, f->calc.q)) { set_error("dtype cannot hold the field's elements"); return GFA_ERR_INVALID; }
     FieldDeviceState *ds;
     int rc = f->ensure_device(nullptr, &ds);

@@ -116,15 +116,19 @@ int gfa_power(gfa_field_t *f, const void *a, int64_t a_stride, const int64_t *ex
 int gfa_scalar_multiply(gfa_field_t *f, const void *a, int64_t a_stride, const int64_t *ks, int64_t k_stride, void *out,
                         int64_t n, int dtype, gfa_stream_t stream);
 /* ufunc.reduce over the last axis of an (n_outer, n_inner) array for op in {ADD, SUB, MUL, DIV}
- * (_domains/_ufunc.py:180-198 allows reduce/accumulate only for the binary ops).  SUB/DIV are left folds. */
+ * (_domains/_ufunc.py:180-198 allows reduce/accumulate only for the binary ops).  SUB/DIV are left folds.
+ * n_outer == 0: GFA_OK, nothing is read or written (the buffers may be null).  n_inner == 0 (no identity is assumed), n_outer > 2^31 - 1 (the
+ * launch grid) or a dtype too narrow for the field: GFA_ERR_INVALID. */
 int gfa_reduce(gfa_field_t *f, int op, const void *a, void *out, int64_t n_outer, int64_t n_inner, int dtype,
                gfa_stream_t stream, int32_t *dev_err);
 
-/* ufunc.accumulate over the last axis of an (n_outer, n_inner) array, same ops and fold conventions as gfa_reduce. */
 /* ufunc.reduceat (dispatched like reduce, _domains/_ufunc.py:689): out[s] = fold of a[starts[s] : ends[s]] with the op; an
  * empty or reversed slice yields a[starts[s]] (NumPy's convention).  starts / ends: device int64 arrays of nseg entries. */
 int gfa_reduceat(gfa_field_t *f, int op, const void *a, const int64_t *starts, const int64_t *ends, int64_t nseg, void *out, int dtype,
                  gfa_stream_t stream, int32_t *dev_err);
+/* ufunc.accumulate over the last axis of an (n_outer, n_inner) array, same ops and fold conventions as gfa_reduce.
+ * n_outer == 0 or n_inner == 0: GFA_OK, nothing is read or written (the buffers may be null); n_outer > 2^31 - 1:
+ * GFA_ERR_INVALID. */
 int gfa_accumulate(gfa_field_t *f, int op, const void *a, void *out, int64_t n_outer, int64_t n_inner, int dtype,
                    gfa_stream_t stream, int32_t *dev_err);
 /* np.convolve(a, b), mode "full": out[k] = sum_i a[i] * b[k-i], na + nb - 1 outputs -- convolve_jit
