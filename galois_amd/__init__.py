@@ -26,6 +26,10 @@ from ._polyfactor import factors  # noqa: E402  (also gives Poly its factorisati
 from ._polyroots import poly_roots_batched, roots_max_terms  # noqa: E402  (also gives Poly its roots() and Roots())
 from ._lagrange import lagrange_poly, lagrange_poly_batched, lagrange_max_points, crt  # noqa: E402
 from ._lfsr import FLFSR, GLFSR, lfsr_step_batched, lfsr_max_order  # noqa: E402
+from ._polyelem import (  # noqa: E402
+    is_primitive_element, primitive_element, primitive_elements, is_normal_element, normal_element, normal_elements,
+    is_primitive_element_batched, is_normal_element_batched,
+)
 from . import _dist as dist  # noqa: E402
 from . import _linalg as linalg  # noqa: E402
 
@@ -37,5 +41,7 @@ __all__ = [
     "is_irreducible_batched", "is_primitive_batched", "poly_divmod_batched", "poly_powmod_batched", "gcd", "egcd", "lcm", "prod",
     "poly_gcd_batched", "poly_egcd_batched", "gcd_max_terms", "poly_roots_batched", "roots_max_terms", "lagrange_poly",
     "lagrange_poly_batched", "lagrange_max_points", "crt", "FLFSR", "GLFSR", "lfsr_step_batched", "lfsr_max_order", "dist", "linalg",
+    "is_primitive_element", "primitive_element", "primitive_elements", "is_normal_element", "normal_element", "normal_elements",
+    "is_primitive_element_batched", "is_normal_element_batched",
 ]
 __version__ = "0.1.0"

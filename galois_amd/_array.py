@@ -116,6 +116,30 @@ class FieldArrayMeta(type):
     def primitive_element(cls):
         return cls(cls._primitive_element_int) if torch.cuda.is_available() else cls._primitive_element_int
 
+    # the three below classify every element of the field in chunks on the device (galois_amd/_polyelem.py); each is computed
+    # once per class and handed out as a copy
+    @property
+    def primitive_elements(cls):
+        """All primitive elements of the field as a sorted 1-D array (_fields/_meta.py:311-348)."""
+        from ._polyelem import field_primitive_elements
+
+        return field_primitive_elements(cls)
+
+    @property
+    def normal_element(cls):
+        """The smallest normal element of GF(p^m) over GF(p) as a scalar, None for a prime field (_fields/_meta.py:351-390)."""
+        from ._polyelem import field_normal_element
+
+        return field_normal_element(cls)
+
+    @property
+    def normal_elements(cls):
+        """All normal elements of GF(p^m) over GF(p) as a sorted 1-D array, empty for a prime field (_fields/_meta.py:393-431).
+        The reference annotates a FieldArray but returns a list of scalars; this is the array."""
+        from ._polyelem import field_normal_elements
+
+        return field_normal_elements(cls)
+
     @property
     def is_prime_field(cls) -> bool:
         return cls._degree == 1

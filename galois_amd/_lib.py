@@ -86,6 +86,8 @@ SIGNATURES = {
                                   c_int, c_void_p, c_void_p]),
     "gfa_charpoly": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_int, c_void_p]),
     "gfa_poly_classify": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_int, _u64p, c_i64, c_i64, c_void_p, c_void_p]),
+    "gfa_poly_element_classify": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_int, _u64p, c_i64, c_i64, c_void_p, c_i64, c_void_p,
+                                          c_void_p]),
     "gfa_poly_divmod": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_void_p, c_int, c_void_p]),
     "gfa_poly_powmod": (c_int, [c_void_p, c_void_p, c_i64, c_i64, _u64p, c_i64, c_void_p, c_i64, c_void_p, c_int, c_void_p]),
     "gfa_poly_gcd": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),

@@ -66,6 +66,15 @@ class Poly:
         return c[int(nz[0].item()):]
 
     @classmethod
+    def _from_trimmed(cls, field, coeffs: FieldArray) -> "Poly":
+        """The Poly of a 1-D array over `field` whose first coefficient is non-zero (or the single coefficient 0), without the
+        checks and the device round trip of _trim: for callers that make many polynomials from rows they have already measured."""
+        p = object.__new__(cls)
+        p._field = field
+        p._coeffs = coeffs
+        return p
+
+    @classmethod
     def Int(cls, integer: int, field=None) -> "Poly":
         """Poly.Int (_polys/_poly.py:372-444): the polynomial whose coefficients are the radix-q digits of the integer."""
         if not isinstance(integer, (int, np.integer)):

@@ -305,6 +305,25 @@ int gfa_charpoly(gfa_field_t *f, const void *a, void *coeffs_out, int64_t batch,
  * below 2^64; beyond that GFA_ERR_UNSUPPORTED.  The host reads nothing back: two launches, the second on the irreducible rows. */
 int gfa_poly_classify(gfa_field_t *f, const void *coeffs, int64_t batch, int64_t degree, int dtype, const uint64_t *cofactor_exps,
                       int64_t n_exps, int64_t exp_limbs, uint8_t *flags_out, gfa_stream_t stream);
+/* is_primitive_element / is_normal_element (_fields/_primitive_element.py:137-166, _fields/_normal_element.py:143-185) of `batch`
+ * residues modulo ONE polynomial: elements is batch x degree device coefficients, row-major, highest degree first; modulus is
+ * degree + 1 device coefficients, highest degree first, monic (the leading coefficient is taken as 1) and irreducible.  Neither
+ * is modified.  flags_out[i] (device): bit 0 = primitive, bit 1 = normal; a bit that was not asked for is 0.
+ *   primitivity is asked for when n_exps > 0 or cofactor_exps != NULL, with the conventions of gfa_poly_classify: HOST memory,
+ *     the n_exps values (q^degree - 1) / r for the prime divisors r of q^degree - 1, each as exp_limbs little-endian 64-bit words
+ *     (q^degree - 1 = 1 has none: a non-null pointer with n_exps == 0).  The zero row is not primitive.
+ *   normality is asked for when normal_mats != NULL and n_mats > 0: n_mats x degree x degree device elements, one row-major
+ *     matrix c_i(Phi) per DISTINCT irreducible factor P_i of x^degree - 1 over GF(q), c_i = (x^degree - 1) / P_i.  ORIENTATION:
+ *     Phi is the matrix of the q-th power acting on column vectors of ASCENDING coefficients, so entry (r, j) of a matrix is the
+ *     contribution of the coefficient of x^j to the coefficient of x^r, and column j of Phi is x^(q j) mod modulus.  A row is
+ *     normal iff no matrix sends it to zero; that is the rank test of the reference (the conjugates are independent).
+ * The irreducibility of the modulus is trusted (the entry point cannot see device memory); for any input the call terminates
+ * inside its buffers, and a stored value that is no field element counts as 0.  Degrees up to 255 over GF(2) (bit-packed), up
+ * to 32 over every other field of order below 2^64; beyond that, and for f == NULL (fields of order >= 2^64 have no gfa_field_t),
+ * GFA_ERR_UNSUPPORTED with a message that names the limits.  At most 2^31 - 1 rows.  The host reads nothing back. */
+int gfa_poly_element_classify(gfa_field_t *f, const void *elements, int64_t batch, const void *modulus, int64_t degree, int dtype,
+                              const uint64_t *cofactor_exps, int64_t n_exps, int64_t exp_limbs, const void *normal_mats, int64_t n_mats,
+                              uint8_t *flags_out, gfa_stream_t stream);
 /* divmod_jit / floordiv_jit / mod_jit (_polys/_dense.py:126-320) for `batch` dividends and ONE divisor: a is batch x na device
  * coefficients, row-major, highest degree first (leading zeros allowed and kept); b is nb coefficients with b[0] != 0 and
  * 1 <= nb <= na.  q_out receives batch x (na - nb + 1) quotient and r_out batch x (nb - 1) remainder coefficients, neither
