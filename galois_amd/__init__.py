@@ -14,9 +14,7 @@ from ._factory import GF, Field  # noqa: E402
 from ._ntt import ntt, intt  # noqa: E402
 from ._codes import BCH, ReedSolomon  # noqa: E402
 from ._poly import Poly, berlekamp_massey  # noqa: E402
-from ._numtheory import (  # noqa: E402
-    is_prime, primitive_root, is_primitive_root, matlab_primitive_poly, conway_poly, primitive_poly,
-)
+from ._numtheory import matlab_primitive_poly, conway_poly, primitive_poly  # noqa: E402
 from ._polysearch import (  # noqa: E402
     irreducible_poly, irreducible_polys, primitive_polys, is_irreducible_batched, is_primitive_batched,
 )
@@ -29,6 +27,14 @@ from ._lfsr import FLFSR, GLFSR, lfsr_step_batched, lfsr_max_order  # noqa: E402
 from ._polyelem import (  # noqa: E402
     is_primitive_element, primitive_element, primitive_elements, is_normal_element, normal_element, normal_elements,
     is_primitive_element_batched, is_normal_element_batched,
+)
+from ._integers import (  # noqa: E402
+    primes, kth_prime, prev_prime, next_prime, random_prime, mersenne_exponents, mersenne_primes, fermat_primality_test,
+    miller_rabin_primality_test, legendre_symbol, jacobi_symbol, kronecker_symbol, perfect_power, trial_division, pollard_p1,
+    pollard_rho, divisors, divisor_sigma, is_prime, is_composite, is_prime_power, is_perfect_power, is_smooth, is_powersmooth, isqrt,
+    iroot, ilog, totatives, euler_phi, mobius, carmichael_lambda, is_cyclic, is_primitive_root, primitive_root, primitive_roots,
+    are_coprime, is_square_free, is_prime_batched, primes_in_range, jacobi_symbol_batched, is_primitive_root_batched,
+    sieve_segment_span,
 )
 from . import _dist as dist  # noqa: E402
 from . import _linalg as linalg  # noqa: E402
@@ -43,5 +49,11 @@ __all__ = [
     "lagrange_poly_batched", "lagrange_max_points", "crt", "FLFSR", "GLFSR", "lfsr_step_batched", "lfsr_max_order", "dist", "linalg",
     "is_primitive_element", "primitive_element", "primitive_elements", "is_normal_element", "normal_element", "normal_elements",
     "is_primitive_element_batched", "is_normal_element_batched",
+    "primes", "kth_prime", "prev_prime", "next_prime", "random_prime", "mersenne_exponents", "mersenne_primes", "fermat_primality_test",
+    "miller_rabin_primality_test", "legendre_symbol", "jacobi_symbol", "kronecker_symbol", "perfect_power", "trial_division",
+    "pollard_p1", "pollard_rho", "divisors", "divisor_sigma", "is_composite", "is_prime_power", "is_perfect_power", "is_smooth",
+    "is_powersmooth", "isqrt", "iroot", "ilog", "totatives", "euler_phi", "mobius", "carmichael_lambda", "is_cyclic", "primitive_roots",
+    "are_coprime", "is_square_free", "is_prime_batched", "primes_in_range", "jacobi_symbol_batched", "is_primitive_root_batched",
+    "sieve_segment_span",
 ]
 __version__ = "0.1.0"

@@ -97,6 +97,12 @@ SIGNATURES = {
     "gfa_lfsr_step": (c_int, [c_void_p, c_int, c_int, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_int, c_void_p]),
     "gfa_lfsr_jump": (c_int, [c_void_p, c_int, c_void_p, c_i64, c_void_p, _u64p, c_i64, c_u64, c_i64, c_void_p, c_int, c_void_p]),
     "gfa_lfsr_max_order": (c_i64, [c_void_p]),
+    "gfa_int_is_prime": (c_int, [c_void_p, c_i64, c_u64, c_u64, c_void_p, c_void_p]),
+    "gfa_int_sieve_segment_span": (c_i64, []),
+    "gfa_int_sieve": (c_int, [c_u64, c_u64, c_void_p, c_i64, c_void_p, c_void_p, c_void_p]),
+    "gfa_int_sieve_expand": (c_int, [c_u64, c_u64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gfa_int_jacobi": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p]),
+    "gfa_int_unit_classify": (c_int, [c_u64, c_void_p, c_i64, c_u64, c_u64, _u64p, c_i64, c_void_p, c_void_p]),
     "gfa_time_matmul":(c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, c_void_p, c_int,
                                 ctypes.POINTER(ctypes.c_float)]),
     "gfa_rs_create": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_u64, c_int, ctypes.POINTER(c_void_p)]),

@@ -419,6 +419,41 @@ int gfa_lfsr_jump(gfa_field_t *f, int kind, const void *P, int64_t n, const void
 /* the largest order gfa_lfsr_jump serves over the field (0 for f == NULL) */
 int64_t gfa_lfsr_max_order(gfa_field_t *f);
 
+/* ---- integer number theory (gfa_integers.hip) ------------------------------------------------------ *
+ * Whole arrays of 64-bit integers, one per lane; no field handle.  Outputs are caller-owned device arrays, nothing is
+ * allocated, synchronised or read back, and count == 0 (an empty window) is GFA_OK with nothing launched.
+ *
+ * is_prime (_prime.py:1401-1458) of `count` integers: values[i] (device, uint64), or start + i step when values == NULL --
+ * GFA_ERR_INVALID when the last of them would pass 2^64 - 1.  flags_out[i] is 1 for a prime, else 0.  Deterministic
+ * Miller-Rabin below 2^64 (bases 2, 325, 9375, 28178, 450775, 9780504, 1795265022). */
+int gfa_int_is_prime(const uint64_t *values, int64_t count, uint64_t start, uint64_t step, uint8_t *flags_out, gfa_stream_t stream);
+/* The integers one workgroup of the sieve owns (a power of two); segment s of a window starts at (start | 1) + s span. */
+int64_t gfa_int_sieve_segment_span(void);
+/* primes (_prime.py:31-97) of the window [start, stop), start <= stop <= 2^40 (GFA_ERR_INVALID beyond), in two steps.
+ * gfa_int_sieve: with B the number of odd integers in the window, bit k < B of bitmap_out (ceil(B / 32) device words, bit k at
+ * bit k & 31 of word k >> 5) is set iff (start | 1) + 2 k is prime, and segment_counts_out[s] is the number of set bits of
+ * segment s, for the ceil(2 B / span) segments.  base_primes: the n_base primes <= sqrt(stop - 1), ascending, on the device
+ * (2 may be among them and is skipped).
+ * gfa_int_sieve_expand: writes the primes of the window in increasing order; segment s starts at
+ * primes_out[segment_offsets[s]] -- the exclusive running sum of the counts, plus 1 when start <= 2 < stop: the entry then
+ * stores 2 at primes_out[0] itself.  primes_out must hold them all. */
+int gfa_int_sieve(uint64_t start, uint64_t stop, const uint32_t *base_primes, int64_t n_base, uint32_t *bitmap_out,
+                  int64_t *segment_counts_out, gfa_stream_t stream);
+int gfa_int_sieve_expand(uint64_t start, uint64_t stop, const uint32_t *bitmap, const int64_t *segment_offsets, int64_t *primes_out,
+                         gfa_stream_t stream);
+/* jacobi_symbol (_prime.py:679-748) of `count` pairs: out[i] in {-1, 0, 1} is (a[i] / n[i n_stride]); a is int64 on the device.
+ * n_stride == 1: n is a device array of odd moduli >= 3 that the caller has validated (an entry that is not reads as symbol 0).
+ * n_stride == 0: ONE modulus for the call, and n points to it in HOST memory -- it is an argument, checked here: even or
+ * below 3 is GFA_ERR_INVALID. */
+int gfa_int_jacobi(const int64_t *a, const uint64_t *n, int64_t count, int64_t n_stride, int8_t *out, gfa_stream_t stream);
+/* Units and primitive roots modulo n >= 1 among `count` integers g = values[i] (device), or start + i step when values == NULL.
+ * flags_out[i] bit 1: gcd(g, n) == 1.  bit 2: g is a unit and g^e != 1 (mod n) for each of the n_exps <= 16 exponents
+ * (HOST memory) -- with phi(n) / r for the primes r | phi(n) that is "g is a primitive root" (_primitive_root.py:102-116).
+ * The powers run modulo n for odd n and modulo n / 2 for n = 2 odd; every other even n with n_exps > 0 is
+ * GFA_ERR_UNSUPPORTED (such n > 4 has no primitive root). */
+int gfa_int_unit_classify(uint64_t n, const uint64_t *values, int64_t count, uint64_t start, uint64_t step, const uint64_t *exps,
+                          int64_t n_exps, uint8_t *flags_out, gfa_stream_t stream);
+
 /* ---- Reed-Solomon -------------------------------------------------------------------------------- *
  * gfa_rs_create replaces the arithmetic part of ReedSolomon.__init__ (_codes/_reed_solomon.py:111-218) and
  * _poly_to_generator_matrix (_codes/_cyclic.py:198-226): roots alpha^(c..c+d-2), g(x), systematic parity matrix.
