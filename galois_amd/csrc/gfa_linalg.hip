@@ -12,6 +12,7 @@
 // correct elimination order gives the same RREF / determinant; the pivot rule above is kept so that L, U and P match
 // the reference entry for entry.
 #include "gfa_internal.h"
+#include "gfa_elim_plan.h"
 
 using namespace gfa;
 
@@ -206,8 +207,8 @@ int dispatch_matmul(const FieldDev &fd, int dtype, const void *a, const void *b,
 // ------------------------------------------------------------------------------------------------
 // Gauss-Jordan / PLU: one workgroup per matrix
 // ------------------------------------------------------------------------------------------------
-constexpr int GJ_THREADS = 256;
-constexpr int GJ_MAX_ROWS = 4096; // column factors are staged in LDS
+using elim_plan::GJ_THREADS;
+using elim_plan::GJ_MAX_ROWS; // column factors are staged in LDS
 
 template <class F>
 __device__ __forceinline__ typename F::elem field_inv(const FieldDev &fd, typename F::elem a)
@@ -542,8 +543,10 @@ int gfa_row_reduce(gfa_field_t *f, void *a, int64_t batch, int64_t m, int64_t n,
     if (!dtype_holds(dtype, f->calc.q)) { set_error("dtype cannot hold the field's elements"); return GFA_ERR_INVALID; }
     if (batch == 0) return GFA_OK;
     if (!rank_out || ((m > 0 && n > 0) && !a)) { set_error("gfa_row_reduce: bad arguments"); return GFA_ERR_INVALID; }
-    if ((m > GJ_MAX_ROWS && !(m * n >= 131072 && batch <= 32)) || n > (1 << 24) || m > (1 << 24)) {
-        set_error("gfa_row_reduce: stacks of matrices are limited to 4096 rows each");
+    if (m > elim_plan::GJ_MAX_DIM || n > elim_plan::GJ_MAX_DIM) { set_error("gfa_row_reduce: matrix too large"); return GFA_ERR_UNSUPPORTED; }
+    const elim_plan::Route route = (m == 0 || n == 0) ? elim_plan::ONE_WORKGROUP : elim_plan::elim_route(batch, m, n);
+    if (route == elim_plan::UNSUPPORTED) {
+        set_error("gfa_row_reduce: stacks of more than 32 matrices are limited to 4096 rows each, smaller stacks to 2097120");
         return GFA_ERR_UNSUPPORTED;
     }
     FieldDeviceState *ds;
@@ -554,8 +557,9 @@ int gfa_row_reduce(gfa_field_t *f, void *a, int64_t batch, int64_t m, int64_t n,
         return GFA_OK;
     }
     const FieldDev fd = f->use_lookup() ? f->lut_desc(*ds) : f->calc;
-    // few large matrices: two kernels per column with the update spread over all CUs; otherwise one workgroup per matrix
-    if (m * n >= 131072 && batch <= 32 && batch <= 65535)
+    // few large (or very tall) matrices: two kernels per column with the update spread over all CUs; otherwise one workgroup per
+    // matrix (gfa_elim_plan.h)
+    if (route == elim_plan::TWO_KERNELS)
         return dispatch_row_reduce_wide(fd, dtype, a, batch, m, n, ncols, (i64 *)rank_out, (hipStream_t)stream);
     return dispatch_row_reduce(fd, dtype, a, batch, m, n, ncols, (i64 *)rank_out, (hipStream_t)stream);
 }
@@ -567,7 +571,7 @@ int gfa_plu_decompose(gfa_field_t *f, void *a, void *l_out, void *p_out, int64_t
     if (!dtype_holds(dtype, f->calc.q)) { set_error("dtype cannot hold the field's elements"); return GFA_ERR_INVALID; }
     if (!pivoting && m - 1 > n) { set_error("gfa_plu_decompose: LU without pivoting needs m - 1 <= n"); return GFA_ERR_INVALID; }
     if (batch == 0) return GFA_OK;
-    if (m > GJ_MAX_ROWS || n > (1 << 24)) { set_error("gfa_plu_decompose: matrix too large (at most 4096 rows)"); return GFA_ERR_UNSUPPORTED; }
+    if (!elim_plan::plu_supported(m, n)) { set_error("gfa_plu_decompose: matrix too large (at most 4096 rows)"); return GFA_ERR_UNSUPPORTED; }
     FieldDeviceState *ds;
     int rc = f->ensure_device(nullptr, &ds);
     if (rc) return rc;

@@ -278,7 +278,8 @@ int gfa_matmul(gfa_field_t *f, const void *a, const void *b, void *out, int64_t 
 /* row_reduce_jit.__call__ (_linalg.py:315-351): Gauss-Jordan elimination IN PLACE on `batch` contiguous (m x n)
  * matrices over the first `ncols` columns; pivot = first non-zero entry at or below the pivot row.  rank_out[b] =
  * number of pivots.  inv_jit / solve_jit / matrix_rank_jit and the row/column/null spaces are host compositions of
- * this call (:480-548, _fields/_array.py:1541-1760).  At most 4096 rows. */
+ * this call (:480-548, _fields/_array.py:1541-1760).  At most 4096 rows per matrix in stacks of more than 32 matrices,
+ * 2097120 rows in smaller ones (csrc/gfa_elim_plan.h); GFA_ERR_UNSUPPORTED beyond. */
 int gfa_row_reduce(gfa_field_t *f, void *a, int64_t batch, int64_t m, int64_t n, int64_t ncols, int64_t *rank_out, int dtype,
                    gfa_stream_t stream);
 /* lu_decompose_jit (pivoting == 0, _linalg.py:354-384) / plu_decompose_jit (pivoting != 0, :387-424) on `batch`

@@ -36,7 +36,7 @@ def u64(a):
 
 
 t_end = time.time() + budget
-n_ntt = n_la = 0
+n_ntt = n_la = n_mid = 0
 while time.time() < t_end:
     if rng.random() < 0.5:
         q = int(NTT_FIELDS[rng.integers(0, len(NTT_FIELDS))])
@@ -85,6 +85,9 @@ while time.time() < t_end:
             n_la += 1
             continue
         m, n, k = (int(v) for v in rng.integers(1, 40, 3))
+        if rng.random() < 0.125:  # one draw in eight: more rows / columns than the 256 threads of the one-workgroup elimination kernels, up to
+            m, n = (int(v) for v in rng.integers(41, 421, 2))  # the first sizes of the two-kernels-per-column route (csrc/gfa_elim_plan.h)
+            n_mid += 1
         A, B = rnd(q, (m, k)), rnd(q, (k, n))
         mk = (lambda a: GF([[int(v) for v in r] for r in a])) if q > 2**63 else (lambda a: GF(a))
         assert np.array_equal(u64((mk(A) @ mk(B)).numpy()), F.matmul(A, B)), ("matmul", q, m, k, n)
@@ -111,4 +114,4 @@ while time.time() < t_end:
         R = rnd(q, (m, n))
         assert np.array_equal(u64(mk(R).row_reduce().numpy()), F.row_reduce(R)[0]), ("row_reduce rect", q, m, n)
         n_la += 1
-print(f"fuzz_ntt_linalg: {n_ntt} transforms and {n_la} matrix cases, every result identical to the oracle (seed {seed}, {budget:.0f} s)")
+print(f"fuzz_ntt_linalg: {n_ntt} transforms and {n_la} matrix cases ({n_mid} with 41..420 rows and columns), every result identical to the oracle (seed {seed}, {budget:.0f} s)")
