@@ -73,6 +73,26 @@ int device_upload(void **out, const void *host, size_t bytes)
     return hip_fail(e, "hipMemcpy of a device table");
 }
 
+namespace {
+__global__ void store_words_kernel(ArgWords a, u64 *dst, int n)
+{
+    const int i = threadIdx.x;
+    if (i < n) dst[i] = a.v[i];
+}
+} // namespace
+
+int upload_words(const u64 *host, size_t n, u64 *dst, hipStream_t st)
+{
+    for (size_t off = 0; off < n; off += ARG_WORDS) {
+        ArgWords a;
+        const int m = (int)std::min<size_t>(ARG_WORDS, n - off);
+        for (int i = 0; i < m; i++) a.v[i] = host[off + i];
+        hipLaunchKernelGGL(store_words_kernel, dim3(1), dim3(ARG_WORDS), 0, st, a, dst + off, m);
+    }
+    GFA_HIP(hipGetLastError());
+    return GFA_OK;
+}
+
 int num_cus()
 {
     static int cached[64] = {0};

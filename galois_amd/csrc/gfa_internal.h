@@ -38,6 +38,14 @@ inline int device_upload(T **out, const std::vector<T> &host)
     return device_upload((void **)out, host.data(), host.size() * sizeof(T));
 }
 
+// A few host words (exponents, schedules) to the device as kernel arguments, ARG_WORDS per one-block launch: ordered on the
+// stream, no synchronous copy.
+constexpr int ARG_WORDS = 256;
+struct ArgWords {
+    u64 v[ARG_WORDS];
+};
+int upload_words(const u64 *host, size_t n, u64 *dst, hipStream_t st);
+
 // compute units of the current device, cached per device (256 when the query fails)
 int num_cus();
 

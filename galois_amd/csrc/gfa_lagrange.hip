@@ -22,24 +22,25 @@
 // (galois_amd/_lagrange.py).
 #include <algorithm>
 
-#include "gfa_internal.h"
+#include "gfa_poly_launch.h"
 #include "gfa_lagrange.h"
 
 using namespace gfa;
-using gfa::polytest::ExtP;
+using namespace gfa::polykit;
 
 namespace {
 
 constexpr int LG_THREADS = 1024;
 // rows of up to this many points share a workgroup of this many threads (tools/bench_lagrange.py)
 constexpr int LG_PACK_THREADS = 256;
-// registers: the digit-vector products and the inversion of GF(p^M) fit 128 registers up to M = 7, 256 up to M = 14
+// This kernel's own limits, tighter than polykit::MaxThreads: it also inverts.  The digit-vector products and the inversion of
+// GF(p^M) fit 128 registers up to M = 7, 256 up to M = 14
 template <class F>
-struct MaxThreads {
+struct LgThreads {
     static constexpr int most = LG_THREADS;
 };
 template <int M>
-struct MaxThreads<ExtP<M>> {
+struct LgThreads<ExtP<M>> {
     static constexpr int most = M >= 15 ? LG_THREADS / 4 : M >= 8 ? LG_THREADS / 2 : LG_THREADS;
 };
 constexpr size_t LG_LDS_BYTES = 150 * 1024;
@@ -47,48 +48,8 @@ constexpr i64 LG_MAX_POINTS(size_t elem) { return (i64)((LG_LDS_BYTES / elem - 1
 
 int lg_pack_threads = LG_PACK_THREADS; // gfa_debug_lagrange_tune
 
-__device__ __forceinline__ u64 load_coeff(const void *p, int dtype, i64 i)
-{
-    switch (dtype) { // uniform over the launch
-    case GFA_U8: return ((const uint8_t *)p)[i];
-    case GFA_U16: return ((const uint16_t *)p)[i];
-    case GFA_U32: return ((const uint32_t *)p)[i];
-    default: return ((const uint64_t *)p)[i];
-    }
-}
-
-__device__ __forceinline__ void store_coeff(void *p, int dtype, i64 i, u64 v)
-{
-    switch (dtype) {
-    case GFA_U8: ((uint8_t *)p)[i] = (uint8_t)v; break;
-    case GFA_U16: ((uint16_t *)p)[i] = (uint16_t)v; break;
-    case GFA_U32: ((uint32_t *)p)[i] = (uint32_t)v; break;
-    default: ((uint64_t *)p)[i] = v; break;
-    }
-}
-
-// the lanes of one row; the barrier is the workgroup's
-struct Team {
-    int tid, n;
-    __device__ __forceinline__ void sync() const { __syncthreads(); }
-};
-
-// a row of x or y in the caller's storage
-struct RowLoad {
-    const void *p;
-    int dtype;
-    i64 base;
-    __device__ __forceinline__ u64 operator[](int i) const { return load_coeff(p, dtype, base + i); }
-};
-struct RowStore {
-    void *p;
-    int dtype;
-    i64 base;
-    __device__ __forceinline__ void set(int i, u64 v) const { store_coeff(p, dtype, base + i, v); }
-};
-
 template <class F>
-__global__ __launch_bounds__(MaxThreads<F>::most) void lg_kernel(FieldDev fd, const void *__restrict__ x, const void *__restrict__ y, i64 batch, int npts, int x_shared,
+__global__ __launch_bounds__(LgThreads<F>::most) void lg_kernel(FieldDev fd, const void *__restrict__ x, const void *__restrict__ y, i64 batch, int npts, int x_shared,
                                                                  int team, void *__restrict__ coeffs_out, int32_t *__restrict__ status_out, int dtype)
 {
     typedef typename F::elem E;
@@ -105,8 +66,6 @@ __global__ __launch_bounds__(MaxThreads<F>::most) void lg_kernel(FieldDev fd, co
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------
-size_t elem_bytes(const FieldDev &fd) { return fd.kind == KIND_PRIME32 || fd.kind == KIND_LUT ? 4 : 8; }
-
 struct LagrangeJob {
     const void *x, *y;
     i64 batch;
@@ -120,7 +79,7 @@ template <class F>
 int launch_lagrange(const FieldDev &fd, const LagrangeJob &j)
 {
     typedef typename F::elem E;
-    const int most = MaxThreads<F>::most, pack = std::min(lg_pack_threads, most);
+    const int most = LgThreads<F>::most, pack = std::min(lg_pack_threads, most);
     int team, threads;
     if (j.npts <= pack) {
         team = 1;
@@ -128,40 +87,17 @@ int launch_lagrange(const FieldDev &fd, const LagrangeJob &j)
         threads = (int)std::min<i64>(pack, (j.batch * team + 63) / 64 * 64); // a small batch does not need the whole workgroup
         threads = std::max(threads, team);
     } else {
-        team = threads = std::min(most, (j.npts + 63) / 64 * 64);
+        team = threads = wave_threads(j.npts, most);
     }
     const int rows = threads / team;
     const size_t lds = (size_t)rows * ((size_t)lagrange::LG_ARRAYS * j.npts + 1) * sizeof(E);
-    auto k = lg_kernel<F>;
-    static bool attr = false;
-    if (!attr) { GFA_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LG_LDS_BYTES)); attr = true; }
+    const int rc = allow_large_lds<lg_kernel<F>>(LG_LDS_BYTES);
+    if (rc) return rc;
     const i64 groups = (j.batch + rows - 1) / rows;
-    hipLaunchKernelGGL(k, dim3((unsigned)groups), dim3(threads), lds, j.st, fd, j.x, j.y, j.batch, j.npts, j.x_shared, team, j.coeffs, j.status, j.dtype);
+    hipLaunchKernelGGL((lg_kernel<F>), dim3((unsigned)groups), dim3(threads), lds, j.st, fd, j.x, j.y, j.batch, j.npts, j.x_shared, team, j.coeffs, j.status, j.dtype);
     GFA_HIP(hipGetLastError());
     return GFA_OK;
 }
-
-template <int M>
-int launch_ext(const FieldDev &fd, const LagrangeJob &j)
-{
-    if constexpr (M > GFA_MAX_EXT_DEGREE) {
-        set_error("gfa_poly_lagrange: unsupported extension degree");
-        return GFA_ERR_UNSUPPORTED;
-    } else {
-        if ((int)fd.m == M) return launch_lagrange<ExtP<M>>(fd, j);
-        return launch_ext<M + 1>(fd, j);
-    }
-}
-
-// the storage type is read through load_coeff, so the kernel is instantiated per field policy only
-template <class F, typename T>
-int launch_lagrange_ft(const FieldDev &fd, const LagrangeJob &j)
-{
-    if constexpr (std::is_same<F, Ext>::value) return launch_ext<2>(fd, j);
-    else return launch_lagrange<F>(fd, j);
-}
-
-int dispatch_lagrange(const FieldDev &fd, int dtype, const LagrangeJob &j) { GFA_DISPATCH_FT(launch_lagrange_ft, fd, dtype, fd, j); }
 
 } // namespace
 
@@ -182,10 +118,9 @@ int gfa_poly_lagrange(gfa_field_t *f, const void *x, const void *y, int64_t batc
     if (batch == 0) return GFA_OK;
     if (!x || !y || !coeffs_out || !status_out) { set_error("gfa_poly_lagrange: bad arguments"); return GFA_ERR_INVALID; }
     if (batch > 0x7fffffff) { set_error("gfa_poly_lagrange: at most 2^31 - 1 rows"); return GFA_ERR_UNSUPPORTED; }
-    FieldDeviceState *ds;
-    const int rc = f->ensure_device(nullptr, &ds);
+    FieldDev fd;
+    const int rc = field_desc(f, &fd);
     if (rc) return rc;
-    const FieldDev fd = f->use_lookup() ? f->lut_desc(*ds) : f->calc;
     const i64 cap = LG_MAX_POINTS(elem_bytes(fd));
     if (npts > cap) {
         set_error("gfa_poly_lagrange: npts = " + std::to_string(npts) + ", the kernel holds a row's points, weights and two pairs of polynomials in LDS up to npts = " +
@@ -193,7 +128,7 @@ int gfa_poly_lagrange(gfa_field_t *f, const void *x, const void *y, int64_t batc
         return GFA_ERR_UNSUPPORTED;
     }
     const LagrangeJob j{x, y, batch, (int)npts, x_rows == 1 && batch > 1 ? 1 : 0, dtype, coeffs_out, status_out, (hipStream_t)stream};
-    return dispatch_lagrange(fd, dtype, j);
+    return for_policy(fd, dtype, "gfa_poly_lagrange", [&](auto p) { return launch_lagrange<typename decltype(p)::type>(fd, j); });
 }
 
 void gfa_debug_lagrange_tune(int pack_threads)

@@ -22,12 +22,12 @@
 //                  The row's exponent exp0 + k stride is formed in LDS by one thread; exp0 arrives as kernel arguments.
 #include <algorithm>
 
-#include "gfa_internal.h"
+#include "gfa_poly_launch.h"
 #include "gfa_lfsr.h"
 
 using namespace gfa;
 using namespace gfa::lfsr;
-using gfa::polytest::ExtP;
+using namespace gfa::polykit;
 
 namespace {
 
@@ -37,51 +37,10 @@ constexpr int LS_BITS_ROWS = 256; // registers per workgroup of ls_bits_kernel
 constexpr size_t LS_LDS_BYTES = 150 * 1024;
 constexpr int LS_EXP_WORDS = 126; // words of exp0 at most; the row's exponent has two more
 constexpr size_t LS_EXP_BYTES = (LS_EXP_WORDS + 2) * sizeof(u64);
-constexpr int LS_JUMP_THREADS = 1024;
 
 constexpr i64 LS_STEP_MAX(size_t elem) { return (i64)((LS_LDS_BYTES / elem - (LS_TILE + 1)) / 2); }
 constexpr i64 LS_JUMP_MAX(size_t elem) { return (i64)(((LS_LDS_BYTES - LS_EXP_BYTES) / elem - 1) / 5); }
 static_assert(jump_elems((int)LS_JUMP_MAX(4)) * 4 + LS_EXP_BYTES <= LS_LDS_BYTES && jump_elems((int)LS_JUMP_MAX(8)) * 8 + LS_EXP_BYTES <= LS_LDS_BYTES, "cap");
-
-template <class F>
-struct MaxThreads { // as gfa_polydiv.hip: the digit-vector products of GF(p^M), M >= 11, need more than 128 registers
-    static constexpr int most = LS_JUMP_THREADS;
-};
-template <int M>
-struct MaxThreads<ExtP<M>> {
-    static constexpr int most = M >= 11 ? LS_JUMP_THREADS / 2 : LS_JUMP_THREADS;
-};
-
-__device__ __forceinline__ u64 load_coeff(const void *p, int dtype, i64 i)
-{
-    switch (dtype) { // uniform over the launch
-    case GFA_U8: return ((const uint8_t *)p)[i];
-    case GFA_U16: return ((const uint16_t *)p)[i];
-    case GFA_U32: return ((const uint32_t *)p)[i];
-    default: return ((const uint64_t *)p)[i];
-    }
-}
-
-__device__ __forceinline__ void store_coeff(void *p, int dtype, i64 i, u64 v)
-{
-    switch (dtype) {
-    case GFA_U8: ((uint8_t *)p)[i] = (uint8_t)v; break;
-    case GFA_U16: ((uint16_t *)p)[i] = (uint16_t)v; break;
-    case GFA_U32: ((uint32_t *)p)[i] = (uint32_t)v; break;
-    default: ((uint64_t *)p)[i] = v; break;
-    }
-}
-
-struct Team { // the workgroup (gfa_polydiv.hip)
-    int tid, n;
-    static constexpr int wave = 64;
-    __device__ __forceinline__ void sync() const { __syncthreads(); }
-    __device__ __forceinline__ void wave_sync() const
-    {
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-    }
-};
 
 template <class E>
 struct Staged { // a lane's row of the output tile
@@ -192,8 +151,6 @@ __global__ __launch_bounds__(MaxThreads<F>::most) void ls_jump_kernel(FieldDev f
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------
-size_t elem_bytes(const FieldDev &fd) { return fd.kind == KIND_PRIME32 || fd.kind == KIND_LUT ? 4 : 8; }
-
 struct StepJob {
     int kind, forward;
     const void *taps;
@@ -212,11 +169,10 @@ int launch_step(const FieldDev &fd, const StepJob &j)
     const size_t elems = LS_LDS_BYTES / sizeof(E);
     const int rows = (int)std::min<size_t>(LS_ROWS, (elems - (size_t)j.n) / ((size_t)j.n + LS_TILE + 1));
     const size_t lds = ((size_t)j.n + (size_t)rows * ((size_t)j.n + LS_TILE + 1)) * sizeof(E);
-    auto k = ls_step_kernel<F>;
-    static bool attr = false;
-    if (!attr) { GFA_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LS_LDS_BYTES)); attr = true; }
+    const int rc = allow_large_lds<ls_step_kernel<F>>(LS_LDS_BYTES);
+    if (rc) return rc;
     const i64 groups = (j.batch + rows - 1) / rows;
-    hipLaunchKernelGGL(k, dim3((unsigned)groups), dim3(LS_ROWS), lds, j.st, fd, j.kind, j.forward, j.taps, j.n, j.states, j.batch, j.steps, rows, j.y, j.dtype);
+    hipLaunchKernelGGL((ls_step_kernel<F>), dim3((unsigned)groups), dim3(LS_ROWS), lds, j.st, fd, j.kind, j.forward, j.taps, j.n, j.states, j.batch, j.steps, rows, j.y, j.dtype);
     GFA_HIP(hipGetLastError());
     return GFA_OK;
 }
@@ -239,48 +195,14 @@ template <class F>
 int launch_jump(const FieldDev &fd, const JumpJob &j)
 {
     typedef typename F::elem E;
-    auto k = ls_jump_kernel<F>;
-    static bool attr = false;
-    if (!attr) { GFA_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LS_LDS_BYTES)); attr = true; }
-    const int threads = std::min((std::max(2 * j.n - 1, 1) + 63) / 64 * 64, MaxThreads<F>::most);
+    const int rc = allow_large_lds<ls_jump_kernel<F>>(LS_LDS_BYTES);
+    if (rc) return rc;
+    const int threads = wave_threads(2 * j.n - 1, MaxThreads<F>::most);
     const size_t lds = LS_EXP_BYTES + jump_elems(j.n) * sizeof(E);
-    hipLaunchKernelGGL(k, dim3((unsigned)j.count), dim3(threads), lds, j.st, fd, j.kind, j.P, j.n, j.state, j.exp0, j.limbs, j.stride, j.out, j.dtype);
+    hipLaunchKernelGGL((ls_jump_kernel<F>), dim3((unsigned)j.count), dim3(threads), lds, j.st, fd, j.kind, j.P, j.n, j.state, j.exp0, j.limbs, j.stride, j.out, j.dtype);
     GFA_HIP(hipGetLastError());
     return GFA_OK;
 }
-
-template <int M, class J>
-int launch_ext(const FieldDev &fd, const J &j)
-{
-    if constexpr (M > GFA_MAX_EXT_DEGREE) {
-        set_error("gfa_lfsr: unsupported extension degree");
-        return GFA_ERR_UNSUPPORTED;
-    } else {
-        if ((int)fd.m == M) {
-            if constexpr (std::is_same<J, StepJob>::value) return launch_step<ExtP<M>>(fd, j);
-            else return launch_jump<ExtP<M>>(fd, j);
-        }
-        return launch_ext<M + 1, J>(fd, j);
-    }
-}
-
-// the storage type is read through load_coeff, so the kernels are instantiated per field policy only
-template <class F, typename T>
-int launch_step_ft(const FieldDev &fd, const StepJob &j)
-{
-    if constexpr (std::is_same<F, Ext>::value) return launch_ext<2, StepJob>(fd, j);
-    else return launch_step<F>(fd, j);
-}
-
-template <class F, typename T>
-int launch_jump_ft(const FieldDev &fd, const JumpJob &j)
-{
-    if constexpr (std::is_same<F, Ext>::value) return launch_ext<2, JumpJob>(fd, j);
-    else return launch_jump<F>(fd, j);
-}
-
-int dispatch_step(const FieldDev &fd, int dtype, const StepJob &j) { GFA_DISPATCH_FT(launch_step_ft, fd, dtype, fd, j); }
-int dispatch_jump(const FieldDev &fd, int dtype, const JumpJob &j) { GFA_DISPATCH_FT(launch_jump_ft, fd, dtype, fd, j); }
 
 bool bad_kind(int kind) { return kind != KIND_FIBONACCI && kind != KIND_GALOIS; }
 
@@ -300,10 +222,9 @@ int gfa_lfsr_step(gfa_field_t *f, int kind, int direction, const void *taps, int
     if (batch == 0 || steps == 0) return GFA_OK;
     if (!taps || !states) { set_error("gfa_lfsr_step: bad arguments"); return GFA_ERR_INVALID; }
     if (batch > 0x7fffffff) { set_error("gfa_lfsr_step: at most 2^31 - 1 registers"); return GFA_ERR_UNSUPPORTED; }
-    FieldDeviceState *ds;
-    const int rc = f->ensure_device(nullptr, &ds);
+    FieldDev fd;
+    const int rc = field_desc(f, &fd);
     if (rc) return rc;
-    const FieldDev fd = f->use_lookup() ? f->lut_desc(*ds) : f->calc;
     hipStream_t st = (hipStream_t)stream;
     if (f->calc.q == 2 && n <= 64 && direction == 1) {
         const i64 groups = (batch + LS_BITS_ROWS - 1) / LS_BITS_ROWS;
@@ -318,15 +239,14 @@ int gfa_lfsr_step(gfa_field_t *f, int kind, int direction, const void *taps, int
         return GFA_ERR_UNSUPPORTED;
     }
     const StepJob j{kind, direction == 1 ? 1 : 0, taps, (int)n, states, batch, steps, y_out, dtype, st};
-    return dispatch_step(fd, dtype, j);
+    return for_policy(fd, dtype, "gfa_lfsr", [&](auto p) { return launch_step<typename decltype(p)::type>(fd, j); });
 }
 
 int64_t gfa_lfsr_max_order(gfa_field_t *f)
 {
     if (!f) return 0;
-    FieldDeviceState *ds;
-    if (f->ensure_device(nullptr, &ds)) return 0;
-    const FieldDev fd = f->use_lookup() ? f->lut_desc(*ds) : f->calc;
+    FieldDev fd;
+    if (field_desc(f, &fd)) return 0;
     return LS_JUMP_MAX(elem_bytes(fd));
 }
 
@@ -346,10 +266,9 @@ int gfa_lfsr_jump(gfa_field_t *f, int kind, const void *P, int64_t n, const void
         set_error("gfa_lfsr_jump: at most 2^31 - 1 rows, and exponents of at most " + std::to_string(LS_EXP_WORDS) + " words");
         return GFA_ERR_UNSUPPORTED;
     }
-    FieldDeviceState *ds;
-    const int rc = f->ensure_device(nullptr, &ds);
+    FieldDev fd;
+    const int rc = field_desc(f, &fd);
     if (rc) return rc;
-    const FieldDev fd = f->use_lookup() ? f->lut_desc(*ds) : f->calc;
     const i64 cap = LS_JUMP_MAX(elem_bytes(fd));
     if (n > cap) {
         set_error("gfa_lfsr_jump: order " + std::to_string(n) + ", the kernel holds the characteristic polynomial, two residues and a product in LDS up to order " +
@@ -358,7 +277,7 @@ int gfa_lfsr_jump(gfa_field_t *f, int kind, const void *P, int64_t n, const void
     }
     JumpJob j{kind, P, (int)n, state, {}, (int)n_limbs, stride, count, states_out, dtype, (hipStream_t)stream};
     for (int l = 0; l < (int)n_limbs; l++) j.exp0.v[l] = exp0_limbs[l];
-    return dispatch_jump(fd, dtype, j);
+    return for_policy(fd, dtype, "gfa_lfsr", [&](auto p) { return launch_jump<typename decltype(p)::type>(fd, j); });
 }
 
 } // extern "C"

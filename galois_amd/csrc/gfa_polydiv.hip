@@ -16,34 +16,22 @@
 //   d = nc - 1 <= PD_POWMOD_MAX(sizeof element) = (150 KiB / sizeof element - 2 K - 1) / 5 = 7654 (32-bit) / 3814 (64-bit elements);
 // above it the entry point returns GFA_ERR_UNSUPPORTED and the caller loops over gfa_convolve and gfa_poly_divmod.
 //
-// The element type is the field policy's (32 bits for Prime32 and Lut, 64 bits otherwise) whatever the storage type, which
-// is read and written through a switch that is uniform over the launch -- so the kernels are instantiated per policy only.
+// The element type is the field policy's (32 bits for Prime32 and Lut, 64 bits otherwise) whatever the storage type, which is
+// read and written through load_coeff / store_coeff.  Those, the workgroup (Team), the thread limits, the policy dispatch and
+// the word upload are the family's: gfa_poly_launch.h.
 #include <algorithm>
 
-#include "gfa_internal.h"
+#include "gfa_poly_launch.h"
 #include "gfa_polydiv.h"
 
 using namespace gfa;
 using namespace gfa::polydiv;
-using gfa::polytest::ExtP;
+using namespace gfa::polykit;
 
 namespace {
 
-// threads of a workgroup at most (a launch takes as many whole waves as it has independent coefficients, up to this): 1024,
-// but 512 for the digit-vector products of GF(p^M), M >= 11, which need more than the 128 registers a 1024-thread workgroup
-// leaves each lane (they would spill to scratch memory)
-constexpr int PD_THREADS = 1024;
-template <class F>
-struct MaxThreads {
-    static constexpr int most = PD_THREADS;
-};
-template <int M>
-struct MaxThreads<ExtP<M>> {
-    static constexpr int most = M >= 11 ? PD_THREADS / 2 : PD_THREADS;
-};
 constexpr size_t PD_DIV_LDS_BYTES = 64 * 1024;
 constexpr size_t PD_POW_LDS_BYTES = 150 * 1024;
-constexpr int PD_ARG_WORDS = 256;
 
 constexpr int PD_POWMOD_MAX(size_t elem) { return (int)((PD_POW_LDS_BYTES / elem - 2 * PD_K - 1) / 5); }
 
@@ -51,63 +39,6 @@ constexpr int PD_POWMOD_MAX(size_t elem) { return (int)((PD_POW_LDS_BYTES / elem
 constexpr size_t div_lds_elems(int nb) { return (size_t)nb + (size_t)(nb - 1 + 2 * PD_K); }
 constexpr size_t pow_lds_elems(int d) { return (size_t)(d + 1) + 2 * (size_t)d + (size_t)std::max(2 * d - 1, d + 2 * PD_K); }
 static_assert(pow_lds_elems(PD_POWMOD_MAX(4)) * 4 <= PD_POW_LDS_BYTES && pow_lds_elems(PD_POWMOD_MAX(8)) * 8 <= PD_POW_LDS_BYTES, "cap");
-
-__device__ __forceinline__ u64 load_coeff(const void *p, int dtype, i64 i)
-{
-    switch (dtype) { // uniform over the launch
-    case GFA_U8: return ((const uint8_t *)p)[i];
-    case GFA_U16: return ((const uint16_t *)p)[i];
-    case GFA_U32: return ((const uint32_t *)p)[i];
-    default: return ((const uint64_t *)p)[i];
-    }
-}
-
-__device__ __forceinline__ void store_coeff(void *p, int dtype, i64 i, u64 v)
-{
-    switch (dtype) {
-    case GFA_U8: ((uint8_t *)p)[i] = (uint8_t)v; break;
-    case GFA_U16: ((uint16_t *)p)[i] = (uint16_t)v; break;
-    case GFA_U32: ((uint32_t *)p)[i] = (uint32_t)v; break;
-    default: ((uint64_t *)p)[i] = v; break;
-    }
-}
-
-struct Source { // coefficients base + i of a storage array
-    const void *p;
-    int dtype;
-    i64 base;
-    __device__ __forceinline__ u64 operator[](int i) const { return load_coeff(p, dtype, base + i); }
-};
-
-struct Sink {
-    void *p;
-    int dtype;
-    i64 base;
-    __device__ __forceinline__ void set(int i, u64 v) const { store_coeff(p, dtype, base + i, v); }
-};
-
-// the workgroup; triangle() runs on its first wave, whose lanes order their LDS and global accesses among themselves
-struct Team {
-    int tid, n;
-    static constexpr int wave = 64;
-    __device__ __forceinline__ void sync() const { __syncthreads(); }
-    __device__ __forceinline__ void wave_sync() const
-    {
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-    }
-};
-
-struct ArgWords {
-    u64 v[PD_ARG_WORDS];
-};
-
-// the exponent reaches the device as kernel arguments: ordered on the stream, no synchronous copy
-__global__ void pd_store_kernel(ArgWords a, u64 *dst, int n)
-{
-    const int i = threadIdx.x;
-    if (i < n) dst[i] = a.v[i];
-}
 
 // divisor and window in LDS
 template <class F>
@@ -122,7 +53,7 @@ __global__ __launch_bounds__(MaxThreads<F>::most) void pd_divmod_lds_kernel(Fiel
     const int nq = na - nb + 1;
     for (int t = g.tid; t < nb; t += g.n) bs[t] = (E)load_coeff(b, dtype, t);
     const Ring<E> W{win, nb - 1 + 2 * PD_K, 0};
-    const Ring<E> R = divide<F, Ring<E>, Lin<E>, Source, Sink, Team>(fd, W, Lin<E>{bs}, Source{a, dtype, row * na}, na, nb, Sink{q_out, dtype, row * nq},
+    const Ring<E> R = divide<F, Ring<E>, Lin<E>, RowLoad, RowStore, Team>(fd, W, Lin<E>{bs}, RowLoad{a, dtype, row * na}, na, nb, RowStore{q_out, dtype, row * nq},
                                                                    q_out != nullptr, true, g);
     if (r_out)
         for (int t = g.tid; t < nb - 1; t += g.n) store_coeff(r_out, dtype, row * (nb - 1) + t, R[t]);
@@ -139,8 +70,8 @@ __global__ __launch_bounds__(MaxThreads<F>::most) void pd_divmod_global_kernel(F
     const i64 row = blockIdx.x;
     const int nq = na - nb + 1;
     const Lin<E> W{ws + row * na};
-    const Lin<E> R = divide<F, Lin<E>, Lin<const E>, Source, Sink, Team>(fd, W, Lin<const E>{bw}, Source{a, dtype, row * na}, na, nb,
-                                                                       Sink{q_out, dtype, row * nq}, q_out != nullptr, true, g);
+    const Lin<E> R = divide<F, Lin<E>, Lin<const E>, RowLoad, RowStore, Team>(fd, W, Lin<const E>{bw}, RowLoad{a, dtype, row * na}, na, nb,
+                                                                       RowStore{q_out, dtype, row * nq}, q_out != nullptr, true, g);
     if (r_out)
         for (int t = g.tid; t < nb - 1; t += g.n) store_coeff(r_out, dtype, row * (nb - 1) + t, R[t]);
 }
@@ -168,7 +99,7 @@ __global__ __launch_bounds__(MaxThreads<F>::most) void pd_powmod_kernel(FieldDev
         for (int j = g.tid; j < d; j += g.n) base[j] = j < d - na ? (E)0 : (E)load_coeff(a, dtype, row * na + j - (d - na));
     } else {
         const Ring<E> W{ps, d + 2 * PD_K, 0};
-        const Ring<E> R = divide<F, Ring<E>, Lin<E>, Source, NoQuotient, Team>(fd, W, C, Source{a, dtype, row * na}, na, nc, NoQuotient(), false, true, g);
+        const Ring<E> R = divide<F, Ring<E>, Lin<E>, RowLoad, NoQuotient, Team>(fd, W, C, RowLoad{a, dtype, row * na}, na, nc, NoQuotient(), false, true, g);
         for (int j = g.tid; j < d; j += g.n) base[j] = R[j];
     }
     g.sync();
@@ -177,12 +108,6 @@ __global__ __launch_bounds__(MaxThreads<F>::most) void pd_powmod_kernel(FieldDev
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------
-int round_up_threads(int work, int most)
-{
-    const int t = (std::max(work, 1) + 63) / 64 * 64;
-    return std::min(t, most);
-}
-
 struct DivJob {
     const void *a, *b;
     i64 batch;
@@ -195,7 +120,7 @@ template <class F>
 int launch_div(const FieldDev &fd, const DivJob &j)
 {
     typedef typename F::elem E;
-    const int threads = round_up_threads(j.nb - 1, MaxThreads<F>::most);
+    const int threads = wave_threads(j.nb - 1, MaxThreads<F>::most);
     const size_t lds = div_lds_elems(j.nb) * sizeof(E);
     if (lds <= PD_DIV_LDS_BYTES) {
         hipLaunchKernelGGL((pd_divmod_lds_kernel<F>), dim3((unsigned)j.batch), dim3(threads), lds, j.st, fd, j.a, j.na, j.b, j.nb, j.q, j.r, j.dtype);
@@ -233,56 +158,10 @@ int launch_pow(const FieldDev &fd, const PowJob &j)
                   std::to_string(PD_POWMOD_MAX(sizeof(E))) + " over this field");
         return GFA_ERR_UNSUPPORTED;
     }
-    auto k = pd_powmod_kernel<F>;
-    static bool attr = false;
-    if (!attr) { GFA_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PD_POW_LDS_BYTES)); attr = true; }
-    const int threads = round_up_threads(2 * d - 1, MaxThreads<F>::most);
-    hipLaunchKernelGGL(k, dim3((unsigned)j.batch), dim3(threads), pow_lds_elems(d) * sizeof(E), j.st, fd, j.a, j.na, j.e, j.limbs, j.c, j.nc, j.out, j.dtype);
-    GFA_HIP(hipGetLastError());
-    return GFA_OK;
-}
-
-template <int M, class J>
-int launch_ext(const FieldDev &fd, const J &j)
-{
-    if constexpr (M > GFA_MAX_EXT_DEGREE) {
-        set_error("gfa_polydiv: unsupported extension degree");
-        return GFA_ERR_UNSUPPORTED;
-    } else {
-        if ((int)fd.m == M) {
-            if constexpr (std::is_same<J, DivJob>::value) return launch_div<ExtP<M>>(fd, j);
-            else return launch_pow<ExtP<M>>(fd, j);
-        }
-        return launch_ext<M + 1, J>(fd, j);
-    }
-}
-
-// the storage type is read through load_coeff, so the kernels are instantiated per field policy only
-template <class F, typename T>
-int launch_div_ft(const FieldDev &fd, const DivJob &j)
-{
-    if constexpr (std::is_same<F, Ext>::value) return launch_ext<2, DivJob>(fd, j);
-    else return launch_div<F>(fd, j);
-}
-
-template <class F, typename T>
-int launch_pow_ft(const FieldDev &fd, const PowJob &j)
-{
-    if constexpr (std::is_same<F, Ext>::value) return launch_ext<2, PowJob>(fd, j);
-    else return launch_pow<F>(fd, j);
-}
-
-int dispatch_div(const FieldDev &fd, int dtype, const DivJob &j) { GFA_DISPATCH_FT(launch_div_ft, fd, dtype, fd, j); }
-int dispatch_pow(const FieldDev &fd, int dtype, const PowJob &j) { GFA_DISPATCH_FT(launch_pow_ft, fd, dtype, fd, j); }
-
-int upload(const uint64_t *h, size_t n, u64 *d, hipStream_t st)
-{
-    for (size_t off = 0; off < n; off += PD_ARG_WORDS) {
-        ArgWords a;
-        const int m = (int)std::min<size_t>(PD_ARG_WORDS, n - off);
-        for (int i = 0; i < m; i++) a.v[i] = h[off + i];
-        hipLaunchKernelGGL(pd_store_kernel, dim3(1), dim3(PD_ARG_WORDS), 0, st, a, d + off, m);
-    }
+    const int rc = allow_large_lds<pd_powmod_kernel<F>>(PD_POW_LDS_BYTES);
+    if (rc) return rc;
+    const int threads = wave_threads(2 * d - 1, MaxThreads<F>::most);
+    hipLaunchKernelGGL((pd_powmod_kernel<F>), dim3((unsigned)j.batch), dim3(threads), pow_lds_elems(d) * sizeof(E), j.st, fd, j.a, j.na, j.e, j.limbs, j.c, j.nc, j.out, j.dtype);
     GFA_HIP(hipGetLastError());
     return GFA_OK;
 }
@@ -301,12 +180,11 @@ int gfa_poly_divmod(gfa_field_t *f, const void *a, int64_t batch, int64_t na, co
     if (batch > 0x7fffffff || na > 0x7fffffff) { set_error("gfa_poly_divmod: at most 2^31 - 1 rows of at most 2^31 - 1 coefficients"); return GFA_ERR_UNSUPPORTED; }
     if (nb == 1) r_out = nullptr; // no remainder coefficients
     if (!q_out && !r_out) return GFA_OK;
-    FieldDeviceState *ds;
-    int rc = f->ensure_device(nullptr, &ds);
+    FieldDev fd;
+    int rc = field_desc(f, &fd);
     if (rc) return rc;
-    const FieldDev fd = f->use_lookup() ? f->lut_desc(*ds) : f->calc;
     const DivJob j{a, b, batch, (int)na, (int)nb, dtype, q_out, r_out, (hipStream_t)stream};
-    return dispatch_div(fd, dtype, j);
+    return for_policy(fd, dtype, "gfa_polydiv", [&](auto p) { return launch_div<typename decltype(p)::type>(fd, j); });
 }
 
 int gfa_poly_powmod(gfa_field_t *f, const void *a, int64_t batch, int64_t na, const uint64_t *exp_limbs, int64_t n_limbs, const void *c, int64_t nc,
@@ -317,18 +195,17 @@ int gfa_poly_powmod(gfa_field_t *f, const void *a, int64_t batch, int64_t na, co
     if (batch == 0) return GFA_OK;
     if (!a || !c || !out) { set_error("gfa_poly_powmod: bad arguments"); return GFA_ERR_INVALID; }
     if (batch > 0x7fffffff || na > 0x7fffffff || nc > 0x7fffffff) { set_error("gfa_poly_powmod: at most 2^31 - 1 rows of at most 2^31 - 1 coefficients"); return GFA_ERR_UNSUPPORTED; }
-    FieldDeviceState *ds;
-    int rc = f->ensure_device(nullptr, &ds);
+    FieldDev fd;
+    int rc = field_desc(f, &fd);
     if (rc) return rc;
-    const FieldDev fd = f->use_lookup() ? f->lut_desc(*ds) : f->calc;
     hipStream_t st = (hipStream_t)stream;
     Scratch ws(st);
     u64 *exps = nullptr;
     GFA_HIP(ws.get(&exps, (size_t)n_limbs));
-    rc = upload(exp_limbs, (size_t)n_limbs, exps, st);
+    rc = upload_words(exp_limbs, (size_t)n_limbs, exps, st);
     if (rc) return rc;
     const PowJob j{a, c, batch, (int)na, (int)nc, dtype, exps, (int)n_limbs, out, st};
-    return dispatch_pow(fd, dtype, j);
+    return for_policy(fd, dtype, "gfa_polydiv", [&](auto p) { return launch_pow<typename decltype(p)::type>(fd, j); });
 }
 
 } // extern "C"

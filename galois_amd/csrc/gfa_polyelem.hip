@@ -11,18 +11,21 @@
 //
 // Two regimes, as gfa_polytest.hip.  GF(2): the residue is W in {1, 2, 4} 64-bit words in registers (degrees 1 .. 255); matrix
 // rows are packed into the same words by a first launch and staged through a 32 KiB slab of LDS.  Every other field served by
-// GFA_DISPATCH_FT: one wave per workgroup; f once (stride 1, read by every lane at the same address), then the lane-strided
+// polykit::for_policy: one wave per workgroup; f once (stride 1, read by every lane at the same address), then the lane-strided
 // columns g, r and t.  After the powers the space of r and t holds the slab of cofactor matrices -- every lane reads the same
 // entry, each its own column of g.  The slab is sized from a 64 KiB budget: with 64-bit elements at m = 32 that is 5 of up to 32
 // matrices per pass.
+//
+// Storage access (load_elem), the policy dispatch and the word upload are the family's: gfa_poly_launch.h.
 #include <algorithm>
 
-#include "gfa_internal.h"
+#include "gfa_poly_launch.h"
 #include "gfa_polyelem.h"
 
 using namespace gfa;
 using namespace gfa::polytest;
 using namespace gfa::polyelem;
+using namespace gfa::polykit;
 
 namespace {
 
@@ -32,32 +35,6 @@ constexpr int PE_MAX_DEGREE_GF2 = 255;
 constexpr size_t PE_LDS_BUDGET = 64 * 1024;
 constexpr int PE_GF2_THREADS = 256;
 constexpr int PE_GF2_SLAB_WORDS = 4096; // 32 KiB: at least 4 matrices (255 rows of 4 words)
-constexpr int PE_ARG_WORDS = 256;
-
-// element i of a device array of the storage type; a value that is no field element reads as 0, so that table-driven
-// arithmetic stays inside its tables whatever the buffers hold
-__device__ __forceinline__ u64 load_elem(const void *p, int dtype, i64 i, u64 q)
-{
-    u64 v;
-    switch (dtype) { // uniform over the launch
-    case GFA_U8: v = ((const uint8_t *)p)[i]; break;
-    case GFA_U16: v = ((const uint16_t *)p)[i]; break;
-    case GFA_U32: v = ((const uint32_t *)p)[i]; break;
-    default: v = ((const uint64_t *)p)[i]; break;
-    }
-    return v < q ? v : 0;
-}
-
-struct ArgWords {
-    u64 v[PE_ARG_WORDS];
-};
-
-// small host arrays reach the device as kernel arguments: ordered on the stream, no synchronous copy
-__global__ void pe_store_kernel(ArgWords a, u64 *dst, int n)
-{
-    const int i = threadIdx.x;
-    if (i < n) dst[i] = a.v[i];
-}
 
 // ---- general fields ------------------------------------------------------------------------------------------------
 template <class F>
@@ -212,40 +189,6 @@ int launch_gf2(const Job &j)
     return GFA_OK;
 }
 
-template <int M>
-int launch_ext(const FieldDev &fd, const Job &j)
-{
-    if constexpr (M > GFA_MAX_EXT_DEGREE) {
-        set_error("gfa_poly_element_classify: unsupported extension degree");
-        return GFA_ERR_UNSUPPORTED;
-    } else {
-        if ((int)fd.m == M) return launch_general<ExtP<M>>(fd, j);
-        return launch_ext<M + 1>(fd, j);
-    }
-}
-
-// the storage type is read through load_elem, so the kernels are instantiated per field policy only
-template <class F, typename T>
-int launch_ft(const FieldDev &fd, const Job &j)
-{
-    if constexpr (std::is_same<F, Ext>::value) return launch_ext<2>(fd, j);
-    else return launch_general<F>(fd, j);
-}
-
-int dispatch(const FieldDev &fd, int dtype, const Job &j) { GFA_DISPATCH_FT(launch_ft, fd, dtype, fd, j); }
-
-int upload(const uint64_t *h, size_t count, u64 *d, hipStream_t st)
-{
-    for (size_t off = 0; off < count; off += PE_ARG_WORDS) {
-        ArgWords a;
-        const int n = (int)std::min<size_t>(PE_ARG_WORDS, count - off);
-        for (int i = 0; i < n; i++) a.v[i] = h[off + i];
-        hipLaunchKernelGGL(pe_store_kernel, dim3(1), dim3(PE_ARG_WORDS), 0, st, a, d + off, n);
-    }
-    GFA_HIP(hipGetLastError());
-    return GFA_OK;
-}
-
 } // namespace
 
 extern "C" {
@@ -269,10 +212,9 @@ int gfa_poly_element_classify(gfa_field_t *f, const void *elements, int64_t batc
     if (!gf2 && degree > PE_MAX_DEGREE) { set_error("gfa_poly_element_classify: degree too large (at most 32 over fields other than GF(2))"); return GFA_ERR_UNSUPPORTED; }
     if (batch == 0) return GFA_OK;
     if (!elements || !modulus || !flags_out) { set_error("gfa_poly_element_classify: bad arguments"); return GFA_ERR_INVALID; }
-    FieldDeviceState *ds;
-    int rc = f->ensure_device(nullptr, &ds);
+    FieldDev fd;
+    int rc = field_desc(f, &fd);
     if (rc) return rc;
-    const FieldDev fd = f->use_lookup() ? f->lut_desc(*ds) : f->calc;
     hipStream_t st = (hipStream_t)stream;
 
     Job j{};
@@ -287,7 +229,7 @@ int gfa_poly_element_classify(gfa_field_t *f, const void *elements, int64_t batc
     const size_t n_words = (size_t)j.n_exps * j.limbs;
     GFA_HIP(ws.get(&dev, std::max<size_t>(n_words, 1)));
     if (n_words) {
-        rc = upload(cofactor_exps, n_words, dev, st);
+        rc = upload_words(cofactor_exps, n_words, dev, st);
         if (rc) return rc;
     }
     j.exps = dev;
@@ -296,7 +238,8 @@ int gfa_poly_element_classify(gfa_field_t *f, const void *elements, int64_t batc
         GFA_HIP(ws.get(&j.packed, (size_t)W * (1 + (size_t)j.n_mats * j.m)));
         return W == 1 ? launch_gf2<1>(j) : W == 2 ? launch_gf2<2>(j) : launch_gf2<4>(j);
     }
-    return dispatch(fd, dtype, j); // the buffers go back to the pool in stream order
+    // the buffers go back to the pool in stream order
+    return for_policy(fd, dtype, "gfa_poly_element_classify", [&](auto p) { return launch_general<typename decltype(p)::type>(fd, j); });
 }
 
 } // extern "C"

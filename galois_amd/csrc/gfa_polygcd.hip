@@ -20,63 +20,21 @@
 // cofactors max(na, nb) product coefficients -- a pair of degree <= 63 is one wave, so many pairs share a compute unit.
 #include <algorithm>
 
-#include "gfa_internal.h"
+#include "gfa_poly_launch.h"
 #include "gfa_polygcd.h"
 
 using namespace gfa;
 using namespace gfa::polydiv;
-using gfa::polytest::ExtP;
+using namespace gfa::polykit;
 
 namespace {
 
-// as gfa_polydiv.hip: 1024 threads at most, 512 for the digit-vector products of GF(p^M), M >= 11 (registers)
-constexpr int PG_THREADS = 1024;
-template <class F>
-struct MaxThreads {
-    static constexpr int most = PG_THREADS;
-};
-template <int M>
-struct MaxThreads<ExtP<M>> {
-    static constexpr int most = M >= 11 ? PG_THREADS / 2 : PG_THREADS;
-};
 constexpr size_t PG_LDS_BYTES = 150 * 1024;
 constexpr size_t PG_SLOT_BYTES = 8; // the reduction word, in front of the coefficients (keeps 64-bit elements aligned)
 
 constexpr i64 PG_MAX_TERMS(size_t elem, bool extended) { return (i64)((PG_LDS_BYTES - PG_SLOT_BYTES) / elem / (extended ? 3 : 1)); }
 constexpr size_t lds_bytes(i64 terms, size_t elem, bool extended) { return PG_SLOT_BYTES + (size_t)terms * (extended ? 3 : 1) * elem; }
 static_assert(lds_bytes(PG_MAX_TERMS(4, false), 4, false) <= PG_LDS_BYTES && lds_bytes(PG_MAX_TERMS(8, true), 8, true) <= PG_LDS_BYTES, "cap");
-
-__device__ __forceinline__ u64 load_coeff(const void *p, int dtype, i64 i)
-{
-    switch (dtype) { // uniform over the launch
-    case GFA_U8: return ((const uint8_t *)p)[i];
-    case GFA_U16: return ((const uint16_t *)p)[i];
-    case GFA_U32: return ((const uint32_t *)p)[i];
-    default: return ((const uint64_t *)p)[i];
-    }
-}
-
-__device__ __forceinline__ void store_coeff(void *p, int dtype, i64 i, u64 v)
-{
-    switch (dtype) {
-    case GFA_U8: ((uint8_t *)p)[i] = (uint8_t)v; break;
-    case GFA_U16: ((uint16_t *)p)[i] = (uint16_t)v; break;
-    case GFA_U32: ((uint32_t *)p)[i] = (uint32_t)v; break;
-    default: ((uint64_t *)p)[i] = v; break;
-    }
-}
-
-// the workgroup, as in gfa_polydiv.hip
-struct Team {
-    int tid, n;
-    static constexpr int wave = 64;
-    __device__ __forceinline__ void sync() const { __syncthreads(); }
-    __device__ __forceinline__ void wave_sync() const
-    {
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-    }
-};
 
 } // namespace
 
@@ -156,38 +114,14 @@ int launch_gcd(const FieldDev &fd, const GcdJob &j)
                   " in LDS up to na + nb = " + std::to_string(cap) + " over this field");
         return GFA_ERR_UNSUPPORTED;
     }
-    auto k = pg_gcd_kernel<F>;
-    static bool attr = false;
-    if (!attr) { GFA_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PG_LDS_BYTES)); attr = true; }
-    const int work = extended ? std::max(j.na, j.nb) : std::min(j.na, j.nb);
-    const int threads = std::min((std::max(work, 1) + 63) / 64 * 64, MaxThreads<F>::most);
-    hipLaunchKernelGGL(k, dim3((unsigned)j.batch), dim3(threads), lds_bytes(terms, sizeof(E), extended), j.st, fd, j.a, j.na, j.b, j.b_shared, j.nb, j.g, j.s, j.t,
+    const int rc = allow_large_lds<pg_gcd_kernel<F>>(PG_LDS_BYTES);
+    if (rc) return rc;
+    const int threads = wave_threads(extended ? std::max(j.na, j.nb) : std::min(j.na, j.nb), MaxThreads<F>::most);
+    hipLaunchKernelGGL((pg_gcd_kernel<F>), dim3((unsigned)j.batch), dim3(threads), lds_bytes(terms, sizeof(E), extended), j.st, fd, j.a, j.na, j.b, j.b_shared, j.nb, j.g, j.s, j.t,
                        j.deg, j.dtype);
     GFA_HIP(hipGetLastError());
     return GFA_OK;
 }
-
-template <int M>
-int launch_ext(const FieldDev &fd, const GcdJob &j)
-{
-    if constexpr (M > GFA_MAX_EXT_DEGREE) {
-        set_error("gfa_poly_gcd: unsupported extension degree");
-        return GFA_ERR_UNSUPPORTED;
-    } else {
-        if ((int)fd.m == M) return launch_gcd<ExtP<M>>(fd, j);
-        return launch_ext<M + 1>(fd, j);
-    }
-}
-
-// the storage type is read through load_coeff, so the kernel is instantiated per field policy only
-template <class F, typename T>
-int launch_gcd_ft(const FieldDev &fd, const GcdJob &j)
-{
-    if constexpr (std::is_same<F, Ext>::value) return launch_ext<2>(fd, j);
-    else return launch_gcd<F>(fd, j);
-}
-
-int dispatch_gcd(const FieldDev &fd, int dtype, const GcdJob &j) { GFA_DISPATCH_FT(launch_gcd_ft, fd, dtype, fd, j); }
 
 } // namespace
 
@@ -208,12 +142,11 @@ int gfa_poly_gcd(gfa_field_t *f, const void *a, int64_t batch, int64_t na, const
     if (batch == 0) return GFA_OK;
     if (!a || !b || !g_out) { set_error("gfa_poly_gcd: bad arguments"); return GFA_ERR_INVALID; }
     if (batch > 0x7fffffff || na > 0x3fffffff || nb > 0x3fffffff) { set_error("gfa_poly_gcd: at most 2^31 - 1 rows of at most 2^30 - 1 coefficients"); return GFA_ERR_UNSUPPORTED; }
-    FieldDeviceState *ds;
-    int rc = f->ensure_device(nullptr, &ds);
+    FieldDev fd;
+    int rc = field_desc(f, &fd);
     if (rc) return rc;
-    const FieldDev fd = f->use_lookup() ? f->lut_desc(*ds) : f->calc;
     const GcdJob j{a, b, batch, (int)na, (int)nb, b_rows == 1 ? 1 : 0, dtype, g_out, s_out, t_out, deg_out, (hipStream_t)stream};
-    return dispatch_gcd(fd, dtype, j);
+    return for_policy(fd, dtype, "gfa_poly_gcd", [&](auto p) { return launch_gcd<typename decltype(p)::type>(fd, j); });
 }
 
 } // extern "C"

@@ -24,25 +24,15 @@
 // above it the entry points return GFA_ERR_UNSUPPORTED and the caller takes the algebraic route (galois_amd/_polyroots.py).
 #include <algorithm>
 
-#include "gfa_internal.h"
+#include "gfa_poly_launch.h"
 #include "gfa_polyroots.h"
 
 using namespace gfa;
-using gfa::polytest::ExtP;
+using namespace gfa::polykit;
 
 namespace {
 
 constexpr int PR_SEARCH_THREADS = 256;
-// as gfa_polygcd.hip: 1024 threads at most, 512 for the digit-vector products of GF(p^M), M >= 11 (registers)
-constexpr int PR_THREADS = 1024;
-template <class F>
-struct MaxThreads {
-    static constexpr int most = PR_THREADS;
-};
-template <int M>
-struct MaxThreads<ExtP<M>> {
-    static constexpr int most = M >= 11 ? PR_THREADS / 2 : PR_THREADS;
-};
 // independent candidates per lane: four chains cover the latency of a product; a digit-vector product is M^2 independent
 // multiplications already
 template <class F>
@@ -58,40 +48,8 @@ constexpr i64 PR_MAX_TERMS(size_t elem) { return (i64)(PR_LDS_BYTES / elem / 4);
 // q (ncoef - 1) batch Horner steps at most in one search: minutes of one launch on a device others share is a hang to them
 constexpr unsigned __int128 PR_MAX_WORK = (unsigned __int128)1 << 42;
 
-__device__ __forceinline__ u64 load_coeff(const void *p, int dtype, i64 i)
-{
-    switch (dtype) { // uniform over the launch
-    case GFA_U8: return ((const uint8_t *)p)[i];
-    case GFA_U16: return ((const uint16_t *)p)[i];
-    case GFA_U32: return ((const uint32_t *)p)[i];
-    default: return ((const uint64_t *)p)[i];
-    }
-}
-
-__device__ __forceinline__ void store_coeff(void *p, int dtype, i64 i, u64 v)
-{
-    switch (dtype) {
-    case GFA_U8: ((uint8_t *)p)[i] = (uint8_t)v; break;
-    case GFA_U16: ((uint16_t *)p)[i] = (uint16_t)v; break;
-    case GFA_U32: ((uint32_t *)p)[i] = (uint32_t)v; break;
-    default: ((uint64_t *)p)[i] = v; break;
-    }
-}
-
-struct Team {
-    int tid, n;
-    __device__ __forceinline__ void sync() const { __syncthreads(); }
-};
-
-// a row of roots_out / of mult_out
-struct RowStore {
-    void *p;
-    int dtype;
-    i64 base;
-    __device__ __forceinline__ void set(int i, u64 v) const { store_coeff(p, dtype, base + i, v); }
-};
-struct RowMult {
-    int32_t *p; // the row
+struct RowMult { // a row of mult_out
+    int32_t *p;
     __device__ __forceinline__ void set(int i, int m) const { p[i] = m; }
 };
 
@@ -172,9 +130,6 @@ __global__ __launch_bounds__(MaxThreads<F>::most) void pr_finish_kernel(FieldDev
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------
-// size of an element of the field policy the descriptor dispatches to (F::elem)
-size_t elem_bytes(const FieldDev &fd) { return fd.kind == KIND_PRIME32 || fd.kind == KIND_LUT ? 4 : 8; }
-
 // does a row with its roots and one quotient fit the finishing kernel's LDS?  Checked before anything is written.
 bool fits_lds(const FieldDev &fd, const char *who, i64 ncoef, i64 nroots)
 {
@@ -216,45 +171,13 @@ int launch_roots(const FieldDev &fd, const RootsJob &j)
                            (u32)chunks, j.roots, j.counter, j.dtype);
         GFA_HIP(hipGetLastError());
     }
-    auto k = pr_finish_kernel<F>;
-    static bool attr = false;
-    if (!attr) { GFA_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PR_LDS_BYTES)); attr = true; }
-    const int threads = std::min((j.nroots + 63) / 64 * 64, MaxThreads<F>::most);
+    const int rc = allow_large_lds<pr_finish_kernel<F>>(PR_LDS_BYTES);
+    if (rc) return rc;
+    const int threads = wave_threads(j.nroots, MaxThreads<F>::most);
     const int lanes = j.mult ? (int)std::min<i64>({(i64)threads, (i64)j.nroots, (room - fixed) / j.ncoef}) : 0;
-    hipLaunchKernelGGL(k, dim3((unsigned)j.batch), dim3(threads), (size_t)(fixed + (i64)lanes * j.ncoef) * sizeof(E), j.st, fd, j.coeffs, j.ncoef, j.roots, j.nroots,
+    hipLaunchKernelGGL((pr_finish_kernel<F>), dim3((unsigned)j.batch), dim3(threads), (size_t)(fixed + (i64)lanes * j.ncoef) * sizeof(E), j.st, fd, j.coeffs, j.ncoef, j.roots, j.nroots,
                        j.counter, j.count, j.mult, lanes, j.dtype);
     GFA_HIP(hipGetLastError());
-    return GFA_OK;
-}
-
-template <int M>
-int launch_ext(const FieldDev &fd, const RootsJob &j)
-{
-    if constexpr (M > GFA_MAX_EXT_DEGREE) {
-        set_error("gfa_poly_roots: unsupported extension degree");
-        return GFA_ERR_UNSUPPORTED;
-    } else {
-        if ((int)fd.m == M) return launch_roots<ExtP<M>>(fd, j);
-        return launch_ext<M + 1>(fd, j);
-    }
-}
-
-// the storage type is read through load_coeff, so the kernels are instantiated per field policy only
-template <class F, typename T>
-int launch_roots_ft(const FieldDev &fd, const RootsJob &j)
-{
-    if constexpr (std::is_same<F, Ext>::value) return launch_ext<2>(fd, j);
-    else return launch_roots<F>(fd, j);
-}
-
-int dispatch_roots(const FieldDev &fd, int dtype, const RootsJob &j) { GFA_DISPATCH_FT(launch_roots_ft, fd, dtype, fd, j); }
-
-int field_desc(gfa_field_t *f, FieldDev *fd)
-{
-    FieldDeviceState *ds;
-    const int rc = f->ensure_device(nullptr, &ds);
-    if (rc) return rc;
-    *fd = f->use_lookup() ? f->lut_desc(*ds) : f->calc;
     return GFA_OK;
 }
 
@@ -289,7 +212,7 @@ int gfa_poly_roots(gfa_field_t *f, const void *coeffs, int64_t batch, int64_t nc
     GFA_HIP(hipMemsetAsync(counter, 0, (size_t)batch * sizeof(u32), st));
     GFA_HIP(hipMemsetAsync(roots_out, 0, ((size_t)batch * (size_t)(ncoef - 1)) << dtype, st)); // the slots; GFA_U8 .. GFA_U64 = 0 .. 3
     const RootsJob j{coeffs, batch, (int)ncoef, (int)ncoef - 1, dtype, roots_out, counter, count_out, mult_out, st};
-    return dispatch_roots(fd, dtype, j);
+    return for_policy(fd, dtype, "gfa_poly_roots", [&](auto p) { return launch_roots<typename decltype(p)::type>(fd, j); });
 }
 
 int gfa_poly_root_multiplicity(gfa_field_t *f, const void *coeffs, int64_t batch, int64_t ncoef, const void *roots, int64_t nroots, int32_t *mult_out, int dtype,
@@ -312,7 +235,7 @@ int gfa_poly_root_multiplicity(gfa_field_t *f, const void *coeffs, int64_t batch
     if (rc) return rc;
     if (!fits_lds(fd, "gfa_poly_root_multiplicity", ncoef, nroots)) return GFA_ERR_UNSUPPORTED;
     const RootsJob j{coeffs, batch, (int)ncoef, (int)nroots, dtype, const_cast<void *>(roots), nullptr, nullptr, mult_out, (hipStream_t)stream};
-    return dispatch_roots(fd, dtype, j);
+    return for_policy(fd, dtype, "gfa_poly_roots", [&](auto p) { return launch_roots<typename decltype(p)::type>(fd, j); });
 }
 
 } // extern "C"

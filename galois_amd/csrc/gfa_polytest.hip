@@ -13,46 +13,26 @@
 // count the first left behind -- the host reads nothing back in between.
 //
 // Two regimes.  GF(2): the candidate and the residue are W in {1, 2, 4} 64-bit words in registers (degrees 1 .. 255).  Every
-// other field served by GFA_DISPATCH_FT (order < 2^64): f, the residue and one work polynomial are lane-strided columns of
+// other field served by polykit::for_policy (order < 2^64): f, the residue and one work polynomial are lane-strided columns of
 // LDS sized by the launch for the degree at hand (degrees 1 .. 32; 3 (m + 1) elements per lane, 50 KiB at m = 32 on 64-bit
 // elements), so nothing is indexed per lane in registers and no kernel needs scratch memory.
+//
+// Storage access (load_coeff), the policy dispatch and the word upload are the family's: gfa_poly_launch.h.
 #include <algorithm>
 
-#include "gfa_internal.h"
-#include "gfa_polytest.h"
+#include "gfa_poly_launch.h"
 
 using namespace gfa;
 using namespace gfa::polytest;
+using namespace gfa::polykit;
 
 namespace {
 
 constexpr int PT_THREADS = 64;        // one wave per workgroup: a lane only ever touches its own LDS column
 constexpr int PT_MAX_DEGREE = 32;     // general fields
 constexpr int PT_MAX_DEGREE_GF2 = 255;
-constexpr int PT_ARG_WORDS = 256;
 
 typedef unsigned long long ull;
-
-__device__ __forceinline__ u64 load_coeff(const void *p, int dtype, i64 i)
-{
-    switch (dtype) { // uniform over the launch
-    case GFA_U8: return ((const uint8_t *)p)[i];
-    case GFA_U16: return ((const uint16_t *)p)[i];
-    case GFA_U32: return ((const uint32_t *)p)[i];
-    default: return ((const uint64_t *)p)[i];
-    }
-}
-
-struct ArgWords {
-    u64 v[PT_ARG_WORDS];
-};
-
-// small host arrays reach the device as kernel arguments: ordered on the stream, no synchronous copy
-__global__ void pt_store_kernel(ArgWords a, u64 *dst, int n)
-{
-    const int i = threadIdx.x;
-    if (i < n) dst[i] = a.v[i];
-}
 
 // ---- general fields ------------------------------------------------------------------------------------------------
 // row `i` of coeffs -> monic f (f[m] = 1) in the lane's LDS column; false when the leading coefficient is zero
@@ -219,28 +199,6 @@ int launch_gf2(const Job &j)
     return GFA_OK;
 }
 
-template <int M>
-int launch_ext(const FieldDev &fd, const Job &j)
-{
-    if constexpr (M > GFA_MAX_EXT_DEGREE) {
-        set_error("gfa_poly_classify: unsupported extension degree");
-        return GFA_ERR_UNSUPPORTED;
-    } else {
-        if ((int)fd.m == M) return launch_general<ExtP<M>>(fd, j);
-        return launch_ext<M + 1>(fd, j);
-    }
-}
-
-// the storage type is read through load_coeff, so the kernels are instantiated per field policy only
-template <class F, typename T>
-int launch_ft(const FieldDev &fd, const Job &j)
-{
-    if constexpr (std::is_same<F, Ext>::value) return launch_ext<2>(fd, j);
-    else return launch_general<F>(fd, j);
-}
-
-int dispatch(const FieldDev &fd, int dtype, const Job &j) { GFA_DISPATCH_FT(launch_ft, fd, dtype, fd, j); }
-
 // q^k as little-endian limbs
 std::vector<u64> big_pow(u64 q, int k, int limbs)
 {
@@ -271,18 +229,6 @@ std::vector<int> rabin_steps(int m)
     return out;
 }
 
-int upload(const std::vector<u64> &h, u64 *d, hipStream_t st)
-{
-    for (size_t off = 0; off < h.size(); off += PT_ARG_WORDS) {
-        ArgWords a;
-        const int n = (int)std::min<size_t>(PT_ARG_WORDS, h.size() - off);
-        for (int i = 0; i < n; i++) a.v[i] = h[off + i];
-        hipLaunchKernelGGL(pt_store_kernel, dim3(1), dim3(PT_ARG_WORDS), 0, st, a, d + off, n);
-    }
-    GFA_HIP(hipGetLastError());
-    return GFA_OK;
-}
-
 } // namespace
 
 extern "C" {
@@ -300,10 +246,9 @@ int gfa_poly_classify(gfa_field_t *f, const void *coeffs, int64_t batch, int64_t
     const bool gf2 = f->calc.q == 2;
     if (gf2 && degree > PT_MAX_DEGREE_GF2) { set_error("gfa_poly_classify: degree too large (at most 255 over GF(2))"); return GFA_ERR_UNSUPPORTED; }
     if (!gf2 && degree > PT_MAX_DEGREE) { set_error("gfa_poly_classify: degree too large (at most 32 over fields other than GF(2))"); return GFA_ERR_UNSUPPORTED; }
-    FieldDeviceState *ds;
-    int rc = f->ensure_device(nullptr, &ds);
+    FieldDev fd;
+    int rc = field_desc(f, &fd);
     if (rc) return rc;
-    const FieldDev fd = f->use_lookup() ? f->lut_desc(*ds) : f->calc;
     hipStream_t st = (hipStream_t)stream;
     const int m = (int)degree;
 
@@ -333,7 +278,7 @@ int gfa_poly_classify(gfa_field_t *f, const void *coeffs, int64_t batch, int64_t
     u64 *dev = nullptr;
     i64 *list = nullptr;
     GFA_HIP(ws.get(&dev, host.size()));
-    rc = upload(host, dev, st);
+    rc = upload_words(host.data(), host.size(), dev, st);
     if (rc) return rc;
     if (j.want_primitive) { // list[0] is the count, the indices follow
         GFA_HIP(ws.get(&list, (size_t)(batch + 1)));
@@ -344,7 +289,7 @@ int gfa_poly_classify(gfa_field_t *f, const void *coeffs, int64_t batch, int64_t
         j.sched = dev; j.exps = dev + exps_at; j.n_exps = (int)n_exps; j.exp_limbs = (int)exp_limbs;
         j.flags = flags_out; j.list = list ? list + 1 : nullptr; j.count = (ull *)list; j.st = st;
         if (gf2) rc = m <= 63 ? launch_gf2<1>(j) : m <= 127 ? launch_gf2<2>(j) : launch_gf2<4>(j);
-        else rc = dispatch(fd, dtype, j);
+        else rc = for_policy(fd, dtype, "gfa_poly_classify", [&](auto p) { return launch_general<typename decltype(p)::type>(fd, j); });
     }
     return rc; // the buffers go back to the pool in stream order
 }
